@@ -19,6 +19,14 @@ timed epoch, so every timed epoch is "epoch W+1" and `ms_per_step` does not depe
 within ~25 epochs, which makes the layer-1 backward product 4x cheaper — a property of the random
 labels, not of the kernels; the free-running figures are reported beside the graded one.)
 
+A plain run sets up, warms up, times the K steps and prints the line below (the headline figures,
+the timed launches' roofline, the graph and its configuration).  `--full` adds everything else the
+bench measures or checks outside the timed region: the CPU baseline, the side epochs (free-running,
+dense loss, cached input product, the other GEMM schemes, upstream's unchanged lines), the
+cache-hostile graph's roofline, measured host synchronisations, the cross-world-size loss check
+and, at N > 1, the self-validation of the sharded run.  `--dump-outputs DIR` writes what the last
+timed step computed (see dump_outputs) before the line is printed.
+
 Printed JSON (rank 0, one line):
   value        = fwd SpMM throughput, nnz(A_hat) / mean duration of the forward `gcn_spmm_csr`
                  launches inside the timed region, in GEdge/s.  At N > 1: all ranks' stored
@@ -28,8 +36,8 @@ Printed JSON (rank 0, one line):
                  pygcn_amd/sharded.py); `spmm_only_gedges` is the same without the exchange.
   ms_per_step  = fwd+bwd ms/epoch (wall, max over ranks)
   roofline     = algorithmic bytes of one forward SpMM launch / its mean duration vs 8 TB/s HBM
-  cpu_baseline = the reference's literal call `torch.spmm(adj, support)` (pygcn/layers.py:34) on
-                 the COO layout the reference builds (pygcn/utils.py:407-414), timed on the box's
+  cpu_baseline = (--full) the reference's literal call `torch.spmm(adj, support)` (pygcn/layers.py:34)
+                 on the COO layout the reference builds (pygcn/utils.py:407-414), timed on the box's
                  host cores on a row block of the same graph; the CSR/MKL form of the same call
                  and the oracle's OpenMP port are reported beside it.
 """
@@ -78,9 +86,17 @@ def parse():
                     help="the timed epoch takes the NLL over ALL vertices (every gradient row is "
                          "non-zero: the fork's live case, a reduction over all nodes — reference "
                          "pygcn/train.py:151-155) instead of upstream's idx_train share")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figures do not need: CPU baseline, side epochs, "
+                         "uniform-graph roofline, host-sync counts, loss check, N > 1 self-validation")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy "
+                         "(float32): the model output (a fixed, seeded sample of its rows when larger "
+                         "than the budget), the loss, and every parameter and its gradient after the step")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the untimed side measurements (free-running and dense-loss epochs)")
+                    help="with --full: skip the untimed side measurements (free-running and dense-loss "
+                         "epochs, other GEMM schemes, upstream's lines, uniform-graph roofline)")
     ap.add_argument("--spmm-only", action="store_true",
                     help="time only forward SpMM launches (profiling aid; not the graded mode)")
     ap.add_argument("--item-cost", type=int, default=0)
@@ -100,8 +116,8 @@ def parse():
                     help="'uniform' (single GPU): the cache-hostile graph — every vertex draws 10 neighbours "
                          "uniformly (+ I, row-normalized): no hubs, every gather an HBM miss")
     ap.add_argument("--no-selfcheck", action="store_true",
-                    help="multi-GPU: skip the pre-timed self-validation (overlap self-test, sharded "
-                         "gradient check against the single-GPU step, link rate)")
+                    help="multi-GPU with --full: skip the pre-timed self-validation (overlap self-test, "
+                         "sharded gradient check against the single-GPU step, link rate)")
     ap.add_argument("--no-overlap", action="store_true",
                     help="multi-GPU: exchange, then one product (no source-block pipelining)")
     ap.add_argument("--compress-hidden", action="store_true",
@@ -289,6 +305,27 @@ def measured_traffic(config, dt):
         return None, f"unreadable: {ex!r}"
 
 
+DUMP_BUDGET_BYTES = 60 << 20        # what --dump-outputs may write in all (the limit is 64 MB)
+
+
+def dump_outputs(directory, out_name, out, whole):
+    """--dump-outputs: `whole` (name -> tensor) in full, and `out` (the step's output, rows of it)
+    in full while it fits in what `whole` leaves of DUMP_BUDGET_BYTES, else a sample of its rows
+    drawn with a fixed seed — so the same arguments give the same inputs and the same sample, and
+    two builds can be compared output for output.  Everything as float32 DIR/<name>.npy."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in whole.items()}
+    room = DUMP_BUDGET_BYTES - sum(a.nbytes for a in arrays.values())
+    rows = out.shape[0]
+    keep = min(rows, max(1, room // (4 * max(1, out[0].numel())))) if rows else 0
+    if keep < rows:
+        pick = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        out = out[torch.from_numpy(pick).to(out.device)]
+    arrays[out_name] = out.detach().float().cpu().numpy()
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` without a launcher: start the N ranks as fresh child processes
     (torch.distributed.run, one per GPU, rendezvous on 127.0.0.1 at a free port) BEFORE this
@@ -443,6 +480,7 @@ def main():
     labels_train = labels[idx_train]
 
     def epoch(dense_loss=False, reference_call=False):
+        """One training epoch; returns what its caller receives: (model output, loss)."""
         model.train()
         opt.zero_grad(set_to_none=True)
         if reference_call:      # upstream's literal lines (train.py:140-157): no `rows=` hint
@@ -452,25 +490,30 @@ def main():
             out = fwd_model(x, adj)
             loss = fwd_model.nll_loss(out.float(), labels, None)
         elif world > 1 and sharded_rows_note is not None:
-            loss = fwd_model.nll_loss(fwd_model(x, adj).float(), labels, idx_train)
+            out = fwd_model(x, adj)
+            loss = fwd_model.nll_loss(out.float(), labels, idx_train)
         elif world > 1:
             # every rank names the rows of its block the loss reads: one autograd node per rank,
             # a static halo of gradient rows (pygcn_amd/sharded_fused.py)
-            loss = fwd_model.nll_loss(fwd_model(x, adj, rows=rows_handle).float(), labels_train)
+            out = fwd_model(x, adj, rows=rows_handle)
+            loss = fwd_model.nll_loss(out.float(), labels_train)
         elif dense_loss:
             # a loss over ALL vertices (the fork's live loss reduces over every node, reference
             # pygcn/train.py:151-155): pygcn_amd.functional.nll_loss = F.nll_loss (mean), whose
             # gradient reaches the model's backward pass in structural form (one non-zero per row)
-            loss = nll_loss(fwd_model(x, adj), labels)
+            out = fwd_model(x, adj)
+            loss = nll_loss(out, labels)
         else:
             # upstream: F.nll_loss(output[idx_train], labels[idx_train]) (train.py:153) — the model is
             # told which rows the loss reads, so the backward pass runs on the rows that can be
             # non-zero (pygcn_amd/fused.py); the forward pass is the full one
-            loss = nll_loss(fwd_model(x, adj, rows=idx_train).float(), labels_train)
+            out = fwd_model(x, adj, rows=idx_train)
+            loss = nll_loss(out.float(), labels_train)
         loss.backward()
         if world > 1:
             fwd_model.allreduce_grads()
         opt.step()
+        return out, loss
 
     snapshot = None
 
@@ -491,14 +534,20 @@ def main():
                     if torch.is_tensor(vv):
                         live[k][kk].copy_(vv)
 
+    last = {} if args.dump_outputs else None      # --dump-outputs: the latest step's result
+
     def step():
         if args.spmm_only:
             with torch.no_grad():
-                spmm_mod.spmm_csr(graph, x)
+                out = spmm_mod.spmm_csr(graph, x)
+            if last is not None:
+                last["spmm_out"] = out
             return
         if snapshot is not None:
             restore_snapshot()
-        epoch(dense_loss=args.dense_loss, reference_call=args.reference_call)
+        out, loss = epoch(dense_loss=args.dense_loss, reference_call=args.reference_call)
+        if last is not None:
+            last.update(log_probs=out, loss=loss)
 
     def timed(k, fn):
         """K calls of fn bracketed by barrier + synchronize; returns (wall seconds, per-call ms from
@@ -548,7 +597,7 @@ def main():
         dist.all_gather_object(names, f"{torch.cuda.get_device_name(dev)} (cuda:{local_rank})")
         selfcheck["devices"] = names
         tol_fwd = 1e-5 if dt == "f32" else 2.0 ** -6
-        if not args.no_selfcheck:
+        if args.full and not args.no_selfcheck:
             try:
                 # (the size must be the same number on both ends: max_rows, not this rank's n_local)
                 selfcheck["link_rate"] = sc.link_rate(dev, min(1_280_000_000, max(1, adj.max_rows) * feat * esize))
@@ -580,7 +629,7 @@ def main():
             selfcheck["exchange_ab_note"] = (
                 "layer-2 forward (GEMM + exchange + local product + log_softmax) per exchange form, 3 "
                 "evaluations after a warm-up, slowest rank's mean; the timed epoch uses the fastest")
-        if not args.no_selfcheck and sharded_rows_note is None and not args.dense_loss \
+        if args.full and not args.no_selfcheck and sharded_rows_note is None and not args.dense_loss \
                 and not args.reference_call:
             # (a) all-reduced gradients of one sharded step vs the same step on ONE GPU (rank 0
             # builds the whole graph next to its shard): the check of the BACKWARD exchange
@@ -621,7 +670,7 @@ def main():
     # the same number at every world size (same graph, features, labels, initial parameters; no
     # dropout in eval mode): a sharded run that computes something else shows up here
     loss_check = None
-    if not args.spmm_only:
+    if args.full and not args.spmm_only:
         model.eval()
         with torch.no_grad():
             out0 = fwd_model(x, adj)
@@ -642,6 +691,15 @@ def main():
         adj.timing = []
     elapsed, per_step = timed(args.steps, step)
     spmm_mod.set_timing_records(None)
+    if last is not None:
+        if rank == 0 and args.spmm_only:
+            dump_outputs(args.dump_outputs, "spmm_out", last["spmm_out"], {})
+        elif rank == 0:
+            whole = {"loss": last["loss"]}
+            for name, p in model.named_parameters():
+                whole[name], whole[name + ".grad"] = p, p.grad
+            dump_outputs(args.dump_outputs, "log_probs", last["log_probs"], whole)
+        last = None
 
     local_ms = {"fwd": 0.0, "bwd": 0.0}
     if world > 1:   # launch window = exchange + local SpMM (the exchange step is part of it)
@@ -744,9 +802,9 @@ def main():
 
     extras = {}
     syncs = None
-    if not args.spmm_only:
+    if args.full and not args.spmm_only:
         syncs = count_host_syncs(step)
-    if not args.spmm_only and not args.no_extras and snapshot is not None:
+    if args.full and not args.spmm_only and not args.no_extras and snapshot is not None:
         snapshot_keep, snapshot = snapshot, None            # free-running: no restore
         _, free = timed(max(args.steps, 8), step)
         extras["ms_per_step_free_running"] = {
@@ -856,7 +914,8 @@ def main():
 
     # the forward product on the CACHE-HOSTILE graph (uniform degree 10 + I: no hubs, every gather an
     # HBM miss), next to the R-MAT figure: is the schedule good, or is R-MAT kind?  
-    if world == 1 and args.graph == "rmat" and not args.no_extras and not args.spmm_only and dt == "f32":
+    if world == 1 and args.graph == "rmat" and args.full and not args.no_extras and not args.spmm_only \
+            and dt == "f32":
         try:
             del model, opt, fwd_model
             snapshot = None
@@ -961,11 +1020,12 @@ def main():
                                    "same epoch on the fp32-equivalent three-part scheme",
                              "exact": "exact: every dense product on hipBLASLt's fp32 path (torch.mm)"}
                             [args.gemm_scheme]) if dt == "f32" else "bf16 MFMA, fp32 accumulate",
-            "host_syncs_per_step": syncs,
-            "host_syncs_note": "MEASURED on one extra epoch of the timed kind after the timed region "
-                               "(torch.cuda.set_sync_debug_mode warnings and hooks on .item() / .tolist() / "
-                               ".cpu() / nonzero, validated against a deliberate .item() first); the "
-                               "dense-loss and upstream-lines epochs carry their own counts",
+            **({"host_syncs_per_step": syncs,
+                "host_syncs_note": "MEASURED on one extra epoch of the timed kind after the timed region "
+                                   "(torch.cuda.set_sync_debug_mode warnings and hooks on .item() / .tolist() / "
+                                   ".cpu() / nonzero, validated against a deliberate .item() first); the "
+                                   "dense-loss and upstream-lines epochs carry their own counts"}
+               if args.full else {}),
             "spmm_fwd_ms": round(t_fwd, 4), "spmm_bwd_ms": round(t_bwd, 4),
             "spmm_bwd_gedges": round(nnz_total / (t_bwd * 1e-3) / 1e9, 4) if bwd_ms else None,
             "spmm_bwd_ms_layer2_layer1": [round(bwd_l2, 4), round(bwd_l1, 4)],
@@ -983,11 +1043,11 @@ def main():
             "spmm_local_fwd_ms_rank0": round(kernel_ms, 4),
             "graph_gen_s": round(t_gen, 2),
             **(dense_bwd_figures(l2 or plain, l1, args.steps) if args.dense_loss and world == 1 else {}),
-            "loss_check": {"value": loss_check,
-                           "what": "eval-mode (no dropout) mean NLL on idx_train at the seeded initial "
-                                   "parameters, before the warm-up: the same graph, features, labels "
-                                   "and parameters at every --gpus N, so this number must agree across "
-                                   "world sizes to fp32 summation order"},
+            **({"loss_check": {"value": loss_check,
+                               "what": "eval-mode (no dropout) mean NLL on idx_train at the seeded initial "
+                                       "parameters, before the warm-up: the same graph, features, labels "
+                                       "and parameters at every --gpus N, so this number must agree across "
+                                       "world sizes to fp32 summation order"}} if args.full else {}),
             **extras,
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
@@ -1024,7 +1084,7 @@ def main():
             line["exchange_exposed_wait_note"] = ("time the compute stream waits for the halo rows "
                                                   "AFTER the own-rows product has run under the "
                                                   "transfers (pipelined dense exchange, rank 0)")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 # the whole graph where it runs in seconds (C3-sized and below), a
                 # 1/8 row block at C4, 1/64 at C5 (bounded CPU work; the sample is named in the line)

@@ -7,6 +7,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,7 +39,7 @@ def test_launcher_passes_a_failing_rank_on_cpu():
 @pytest.mark.gpu
 def test_bench_starts_its_own_ranks():
     r, _ = _run(["--gpus", "2", "--rehearsal", "--config", "c3", "--steps", "2", "--warmup", "1",
-                 "--no-extras"], 900)
+                 "--full", "--no-extras"], 900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -59,7 +60,7 @@ def test_bench_starts_its_own_ranks():
     assert all(v <= 1e-5 for v in sc["exchange_ab_max_err_vs_halo"].values())
     assert sc["link_rate"]["gb_per_s"] > 0
     # the same problem at every world size: the single-GPU run must print the same eval loss
-    r1, _ = _run(["--gpus", "1", "--config", "c3", "--steps", "1", "--warmup", "0", "--no-extras",
+    r1, _ = _run(["--gpus", "1", "--config", "c3", "--steps", "1", "--warmup", "0", "--full", "--no-extras",
                   "--no-cpu-baseline"], 900)
     assert r1.returncode == 0, r1.stderr[-2000:]
     one = json.loads([ln for ln in r1.stdout.splitlines() if ln.startswith("{")][-1])
@@ -82,8 +83,8 @@ def test_bench_dense_loss_mode_and_measured_fields():
     """`bench.py --dense-loss` (the loss over all vertices as the timed epoch) and the fields the
     line must carry: measured host synchronisations, the full-height transpose product as a
     GEdge/s + roofline pair, the GEMM scheme, the cross-world-size loss check."""
-    r, _ = _run(["--config", "tiny", "--dense-loss", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                 "--no-extras"], 600)
+    r, _ = _run(["--config", "tiny", "--dense-loss", "--steps", "2", "--warmup", "1", "--full",
+                 "--no-cpu-baseline", "--no-extras"], 600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["config"]["mode"] == "train-epoch (loss over all vertices)"
@@ -91,7 +92,7 @@ def test_bench_dense_loss_mode_and_measured_fields():
     assert line["spmm_bwd_dense_gedges"] > 0 and line["spmm_bwd_dense_roofline_frac"] > 0
     assert line["gemm_scheme"].startswith("bf16x3") and line["loss_check"]["value"] > 0
     assert line["roofline"]["bound"] == "hbm" and line["unit"] == "GEdge/s"
-    r2, _ = _run(["--config", "tiny", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], 600)
+    r2, _ = _run(["--config", "tiny", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"], 600)
     assert r2.returncode == 0, r2.stderr[-2000:]
     full = json.loads([ln for ln in r2.stdout.splitlines() if ln.startswith("{")][-1])
     for key in ("ms_per_step_dense_loss", "host_syncs_per_step_dense_loss", "ms_per_step_reference_call",
@@ -108,7 +109,7 @@ def test_bench_explicit_exchange_and_scheme_flags():
     """`--exchange rccl-allgather` (the north star's literal collective for the activations), `--gemm-scheme
     h2` and `--graph uniform` are accepted and named in the line."""
     r, _ = _run(["--gpus", "2", "--rehearsal", "--config", "tiny", "--steps", "1", "--warmup", "1",
-                 "--no-extras", "--exchange", "rccl-allgather", "--gemm-scheme", "h2"], 900)
+                 "--full", "--no-extras", "--exchange", "rccl-allgather", "--gemm-scheme", "h2"], 900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["exchange_chosen"] == "rccl-allgather" and "exchange_ab_ms" not in line
@@ -119,3 +120,37 @@ def test_bench_explicit_exchange_and_scheme_flags():
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert "UNIFORM" in line["config"]["workload"] and line["value"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """A plain run times exactly --steps epochs and runs nothing that only --full needs;
+    --dump-outputs writes the last timed step's results (float32, within 64 MB), and the same
+    arguments give the same inputs, so two runs agree output for output."""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r, _ = _run(["--config", "tiny", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)], 600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert len(line["ms_per_step_min_max"]) == 2 and line["value"] > 0 and line["unit"] == "GEdge/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "f32"
+        for key in ("cpu_baseline", "loss_check", "host_syncs_per_step", "ms_per_step_free_running",
+                    "ms_per_step_dense_loss", "roofline_uniform"):
+            assert key not in line, key
+        files = {f.name: np.load(f) for f in d.iterdir()}
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 * 10 ** 6
+        assert all(a.dtype == np.float32 for a in files.values())
+        names = {"log_probs.npy", "loss.npy"} | {f"gc{i}.{p}{g}.npy" for i in (1, 2)
+                                                 for p in ("weight", "bias") for g in ("", ".grad")}
+        assert set(files) == names, sorted(files)
+        n_train = max(1, int(50_000 * 140 / 2708))
+        assert files["log_probs.npy"].shape == (n_train, 256)
+        assert np.isfinite(files["log_probs.npy"]).all() and files["loss.npy"] > 0
+        dumps.append(files)
+    for name, a in dumps[0].items():
+        b = dumps[1][name]
+        assert np.abs(a - b).max() <= 1e-5 * np.abs(a).max(), name
