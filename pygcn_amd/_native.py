@@ -6,7 +6,7 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# (GCN_SPMM_LIB: an experiment build of the same ABI — tools/*_variant_sweep.py; never set in product use)
+# (GCN_SPMM_LIB: an experiment build of the same ABI — tools/build_gemm_variant.sh; never set in product use)
 LIB_PATH = os.environ.get("GCN_SPMM_LIB") or os.path.join(_HERE, "csrc", "libgcn_spmm.so")
 
 GCN_ABI_VERSION = 25

@@ -30,7 +30,6 @@ def build(force=False, verbose=True):
     #  warning per inlined copy, a thousand per build)
     flags = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-Wno-inline-asm", "-I",
              os.path.join(ROOT, "include")]
-    flags[0:0] = os.environ.get("PYGCN_HIPCC_FLAGS", "").split()    # tuning experiments only
     objdir = os.path.join(HERE, "csrc", "build")
     os.makedirs(objdir, exist_ok=True)
     jobs = []

@@ -53,6 +53,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
 
 #include "gcn_spmm.h"
 
@@ -80,16 +81,10 @@ constexpr int kChunk = 16;                         // K per MFMA 32x32x16
 constexpr int kChunks = kK / kChunk;               // 16
 constexpr int kFragBytes = 64 * 16;                // one B fragment: 64 lanes x 8 bf16
 constexpr int kChunkBytes = 3 * 8 * kFragBytes;    // 3 splits x 8 column blocks = 24 KiB
-#ifndef GEMM_WAVES
-#define GEMM_WAVES 8
-#endif
-constexpr int kWaves = GEMM_WAVES;                 // waves per workgroup, 32 rows each
+constexpr int kWaves = 8;                          // waves per workgroup, 32 rows each
 constexpr int kThreads = 64 * kWaves;
 constexpr int kTileRows = 32 * kWaves;
-#ifndef GEMM_STAGE
-#define GEMM_STAGE 2
-#endif
-constexpr int kStage = GEMM_STAGE;                 // K steps of W staged per barrier
+constexpr int kStage = 2;                          // K steps of W staged per barrier
 constexpr int kStageBytes = kStage * kChunkBytes;
 constexpr int kWLoads = kStageBytes / 16 / kThreads;   // 16-byte pieces of a W stage per thread
 
@@ -306,13 +301,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_kernel(const float *__
 // subnormal): the absolute error per element is bounded by 2^-38 · max|X|; inputs with a wider
 // dynamic range that matters should use the 3 x bf16 entry point.  Optionally the kernel reports
 // max|Y| (one atomic max per wave) — the next layer's bound.
-#ifndef GEMM_H2_RING
-#define GEMM_H2_RING 4
-#endif
-#ifndef GEMM_H2_GRID
-#define GEMM_H2_GRID 256          /* persistent workgroups: one per CU */
-#endif
-constexpr int kH2Ring = GEMM_H2_RING;                      // X ring: steps in flight + 1
+constexpr int kXwGrid = 256;                               // persistent workgroups: one per CU
 constexpr int kH2ChunkBytes = 2 * 8 * kFragBytes;          // 2 splits x 8 column blocks = 16 KiB
 constexpr int kH2StageBytes = kStage * kH2ChunkBytes;
 constexpr int kH2WLoads = kH2StageBytes / 16 / kThreads;
@@ -498,9 +487,9 @@ template <int N> __device__ __forceinline__ void dma_wait()
 // EPI 0: plain product; EPI 2: backward mask in the store (its own instantiation, so that no branch
 // surrounds the mask loads: they are requested one column block AHEAD, before the current block's
 // stores, and the wait for them leaves only those stores outstanding — fetched where they were used
-// they cost one drain of all earlier stores per column block); both persistent with the cross-tile pipeline.
-// EPI 1 (FWD_EPI): bias + ReLU + Philox dropout in the store; the Philox state would not fit next to
-// the next tile's prefetched fragments (spills), so this instantiation runs one tile per workgroup.
+// they cost one drain of all earlier stores per column block).
+// EPI 1, 4-6 (FWD_EPI): bias + ReLU + Philox dropout in the store, the bias and the seed staged once
+// per workgroup.  Every instantiation is persistent with the cross-tile pipeline.
 #ifdef GEMM_PROFILE_STAMPS   /* experiment builds only (tools/gemm_stamps_probe.py): where a tile's cycles go */
 __device__ unsigned long long g_gemm_stamps[8];
 __device__ unsigned long long g_gemm_step_stamps[16];
@@ -542,9 +531,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_h2_kernel(
     // pipeline runs ACROSS tile boundaries — the X fragments of the next tile's first steps and
     // its first W stage are already in flight while the current tile's last steps are multiplied
     // and its 128 accumulator registers are stored, so no tile pays a cold prologue (with one
-    // workgroup per CU nothing else would cover it).  The X ring has kH2Ring slots with static
-    // indices; kChunks % kH2Ring == 0 keeps slot = step % kH2Ring valid across the boundary.
-    static_assert(kChunks % kH2Ring == 0, "the X ring must divide the K steps of a tile");
+    // workgroup per CU nothing else would cover it).
     static_assert(kChunks % KS == 0 && (kChunks / KS) % 2 == 0, "W stages must alternate evenly");
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * kSchStageBytes];    // the W stage buffers
     // (a separate LDS object, so the compiler's wait-count pass can tell a DMA into an X ring from
@@ -600,17 +587,10 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_h2_kernel(
     const uint32_t w_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)lds +
                            __builtin_amdgcn_readfirstlane(wave) * SK::WShare;
     // this wave's eighth (h2: 4 KiB = 4 DMA instructions, b3: 3) of W stage `st` -> W buffer `b`
-#ifndef GEMM_ABLATE_WPIECES    /* ablation builds only (results garbage): DMA instructions per wave and W stage */
-#define GEMM_ABLATE_WPIECES (-1)
-#endif
-    [[maybe_unused]] bool ablate_first_tile = GEMM_ABLATE_WPIECES >= 0;
     auto w_issue = [&](int st, int b) {
         const unsigned char *src = wl + (size_t)st * kSchStageBytes + wave * SK::WShare + lane * 16;
-        constexpr int kPieces = GEMM_ABLATE_WPIECES >= 0 ? GEMM_ABLATE_WPIECES : SK::WShare / 1024;
 #pragma unroll
-        for (int i = 0; i < SK::WShare / 1024; ++i)      // (ablation: all pieces during a workgroup's FIRST tile, so
-            if (i < kPieces || ablate_first_tile)        //  that the stale W stages the later tiles multiply are real data)
-                dma16(src + i * 1024, w_lds + b * kSchStageBytes + i * 1024);
+        for (int i = 0; i < SK::WShare / 1024; ++i) dma16(src + i * 1024, w_lds + b * kSchStageBytes + i * 1024);
     };
     unsigned char *xl = xlds + __builtin_amdgcn_readfirstlane(wave) * (kXRing * kXChunkBytes);
     // (what this lane FETCHES in instruction j of a chunk, and where this MFMA lane READS)
@@ -699,11 +679,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_h2_kernel(
     GEMM_STAMP(st_begin);
     for (; tile < n_tiles; tile += gridDim.x) {
         GEMM_STAMP(st_a);
-#ifndef GEMM_H2_EPI_PERSIST
-#define GEMM_H2_EPI_PERSIST 1
-#endif
-        if (GEMM_ABLATE_WPIECES >= 0 && tile != (int64_t)blockIdx.x) ablate_first_tile = false;
-        const bool has_next = (!FWD_EPI || GEMM_H2_EPI_PERSIST) && tile + gridDim.x < n_tiles;   // (uniform)
+        const bool has_next = tile + gridDim.x < n_tiles;   // (uniform)
         // the W image's 32 load addresses are loop-invariant; left visible, hipcc hoists all of
         // them out of the tile loop as 64-bit VGPR pairs and spills 50 registers
         asm volatile("" : "+s"(wl));
@@ -818,9 +794,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_h2_kernel(
                         v.z = m.z > 0.f ? v.z * mask_scale : 0.f;
                         v.w = m.w > 0.f ? v.w * mask_scale : 0.f;
                     }
-#ifdef GEMM_H2_ABLATE_STORES      /* ablation build only: keeps the arithmetic, drops the traffic */
-                    if (v.x == 1.2345e-30f)
-#endif
                     *(f32x4 *)(yrow + 32 * nb + 8 * g) = v;
                     if (y_absmax != nullptr) {                                 // (wave-uniform)
                         if (RELU)                    // stored values are >= 0 (or NaN): the bits as they are
@@ -983,7 +956,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_h2_kernel(
 //     16 bytes, a store instruction covers 16 rows x 64 contiguous bytes): 64 accumulator registers;
 //   * the previous tile's results stay in 64 registers (`prev`) and leave one column block at a time,
 //     two per K stage, BETWEEN the stage's MFMA groups;
-//   * NOTHING is issued as a burst (S16_SPREAD; the burst form of the same kernel runs 6.7 ms): behind
+//   * NOTHING is issued as a burst (the burst form of the same kernel ran 6.7 ms): behind
 //     column block 0 / 2 / 4 of a stage go two W pieces each, behind 6 the X chunk, behind 8 and 10 one
 //     store each, behind 12 the next chunk is waited for (a counted wait: it was issued a stage ago) and
 //     split into the other fragment set, under the last column blocks' MFMAs;
@@ -1092,12 +1065,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_s16_kernel(
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)s16_lds;
     const uint32_t w_lds = lds0 + wave * kWShare;
     const uint32_t lane16 = (uint32_t)lane * 16u;
-#ifndef S16_ABLATE        /* ablation builds only (results garbage): 1 no stores, 2 W staged during the first tile only, 4 X likewise */
-#define S16_ABLATE 0
-#endif
-#ifndef S16_SPREAD       /* 0 (experiment builds): a stage's DMA and stores as a burst behind the barrier, its split at the end */
-#define S16_SPREAD 1
-#endif
     // this wave's eighth of W stage `st` (6 DMA instructions; the immediate moves BOTH ends, see dma16_s): pieces 2 pr, 2 pr + 1
     auto w_issue_pair = [&](int st, int b, int pr) {
         const unsigned char *src = wl + (size_t)st * kSt + wave * kWShare;
@@ -1168,7 +1135,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_s16_kernel(
         dst[0] = w.x;
         dst[1] = w.y;
     };
-    auto bits_store = [&](int64_t t) {                           // after the tile's 16th column block
+    auto write_keep_bits = [&](int64_t t) {                      // after the tile's 16th column block
         if (BITS) *(uint2 *)(ep.keep_bits_out + (t * kS16Rows + lrow) * 8 + 2 * q) = uint2{kb[0], kb[1]};
     };
     [[maybe_unused]] int64_t pmask_row = 0;                      // masked form: the mask row of this lane's prev row
@@ -1283,33 +1250,31 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_s16_kernel(
                     const int64_t drow = ptile * kS16Rows + lrow + ep.drop_row_base;
                     const int cb = 2 * c + u;
                     const f32x4 v = finish(cb, prev[cb], mk[u], drow);
-                    if (!(S16_ABLATE & 1) || v.x == 1.2345e-30f) *(f32x4 *)(ybase + yoff + 16 * cb) = v;
-                    if (cb == 15) bits_store(ptile);
+                    *(f32x4 *)(ybase + yoff + 16 * cb) = v;
+                    if (cb == 15) write_keep_bits(ptile);
                 }
             };
             auto stores = [&]() __attribute__((always_inline)) { store_one(0); store_one(1); };
             // masked form: the masks were loaded a stage ago, and the compiler's wait for them must not
             // see this stage's DMA (it cannot count inline-assembly loads): stores first, then the next
-            // pair's mask loads, then the DMA.  Other forms: DMA first, the stores are the youngest.
+            // pair's mask loads, then the DMA as a burst.  Other forms (SPREAD): DMA and stores between
+            // the column blocks below, the stores the youngest.
             if (MASKED) {
                 stores();
                 if (c + 1 < kS16Stages) { if (have_prev) mask_load(c + 1); }
             }
             const bool issued_w = (c + 1 < kS16Stages) || has_next;
             const bool issued_x = (c + 2 < kS16Stages) || has_next;
-            constexpr bool SPREAD = S16_SPREAD && !MASKED;          // (MASK_BITS loads nothing in its stages: it spreads)
+            constexpr bool SPREAD = !MASKED;          // (MASK_BITS loads nothing in its stages: it spreads)
             auto w_issue_all = [&]() {
                 if (c + 1 < kS16Stages) w_issue(c + 1, (c + 1) & 1);
                 else if (has_next) w_issue(0, 0);                // the next tile's first stage
             };
-            const bool first_tile = tile == (int64_t)blockIdx.x;
             auto issue_w_pair = [&](int pr) {
-                if ((S16_ABLATE & 2) && !first_tile) return;
                 if (c + 1 < kS16Stages) w_issue_pair(c + 1, (c + 1) & 1, pr);
                 else if (has_next) w_issue_pair(0, 0, pr);
             };
             auto issue_x = [&]() {
-                if ((S16_ABLATE & 4) && !first_tile) return;
                 if (c + 2 < kS16Stages)       // chunk c + 2 into the ring slot chunk c left (split a stage ago)
                     x_issue(tile, c + 2, c & 1);
                 else if (has_next)
@@ -1318,7 +1283,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_s16_kernel(
             if (!SPREAD) {
                 w_issue_all();
                 issue_x();
-                if (!MASKED) stores();
             }
             const unsigned char *buf = lds + (c & 1) * kSt;
             const u32x4 (&Xp)[3] = Xq[c & 1];
@@ -1346,25 +1310,14 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_s16_kernel(
                 // SPREAD: nothing is issued as a burst.  Behind column block 0 / 2 / 4: two W pieces each;
                 // 6: the X chunk; 8, 10: one store each; 12: the next chunk (issued a stage ago) is waited
                 // for and split into the other fragment set, under the last column blocks' MFMAs.
-#ifndef S16_SCHED         /* experiment builds: other placements of the same pieces (all issue in the same ORDER) */
-#define S16_SCHED 0
-#endif
-                // (column block behind which go: W pairs 0-2, the X chunk, store 0, store 1, the split)
-                constexpr int at[7] = {S16_SCHED == 0 ? 0 : S16_SCHED == 1 ? 1 : S16_SCHED == 2 ? 0 : 2,
-                                       S16_SCHED == 0 ? 2 : S16_SCHED == 1 ? 3 : S16_SCHED == 2 ? 1 : 4,
-                                       S16_SCHED == 0 ? 4 : S16_SCHED == 1 ? 5 : S16_SCHED == 2 ? 2 : 6,
-                                       S16_SCHED == 0 ? 6 : S16_SCHED == 1 ? 7 : S16_SCHED == 2 ? 4 : 8,
-                                       S16_SCHED == 0 ? 8 : S16_SCHED == 1 ? 9 : S16_SCHED == 2 ? 7 : 10,
-                                       S16_SCHED == 0 ? 10 : S16_SCHED == 1 ? 11 : S16_SCHED == 2 ? 10 : 12,
-                                       S16_SCHED == 0 ? 12 : S16_SCHED == 1 ? 13 : S16_SCHED == 2 ? 13 : 14};
                 if (SPREAD) {
-                    if (cb == at[0]) issue_w_pair(0);
-                    if (cb == at[1]) issue_w_pair(1);
-                    if (cb == at[2]) issue_w_pair(2);
-                    if (cb == at[3]) issue_x();
-                    if (cb == at[4]) store_one(0);
-                    if (cb == at[5]) store_one(1);
-                    if (cb == at[6] && issued_w) {
+                    if (cb == 0) issue_w_pair(0);
+                    if (cb == 2) issue_w_pair(1);
+                    if (cb == 4) issue_w_pair(2);
+                    if (cb == 6) issue_x();
+                    if (cb == 8) store_one(0);
+                    if (cb == 10) store_one(1);
+                    if (cb == 12 && issued_w) {
                         // younger than the chunk's two DMA instructions (at least): this stage's 6 W pieces,
                         // its X chunk and its stores
                         if (issued_x) { if (have_prev) dma_wait<10>(); else dma_wait<8>(); }
@@ -1416,7 +1369,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_s16_kernel(
             }
             if (DROP16) __builtin_amdgcn_sched_barrier(0);
         }
-        bits_store(ptile);
+        write_keep_bits(ptile);
     }
     if (y_absmax != nullptr) {
 #pragma unroll
@@ -1727,8 +1680,8 @@ __global__ __launch_bounds__(256) void order_w_bf16_kernel(const uint16_t *__res
 // multiplies its 64 x 128 block of the result (2 x 4 tiles) over the super-step's two MFMA steps.
 // (Round 3, first form: 64 columns of one row per instruction, 4 bytes per lane.  The address unit
 //  takes as long for such a wave instruction as for a 16-byte one, all waves issue their loads at
-//  the same point of the step, and the ablation builds showed load phase and arithmetic adding up
-//  instead of overlapping: 5.5 ms = 2.9 ms without loads + 2.6 ms — tools/atg_variant_sweep.py.)
+//  the same point of the step, and ablation builds showed load phase and arithmetic adding up
+//  instead of overlapping: 5.5 ms = 2.9 ms without loads + 2.6 ms.)
 // Loads run kAtgDepth super-steps ahead in a register ring.  The row list is cut into slabs, one
 // per workgroup; the slabs' partial products are added in slab order by a second kernel
 // (deterministic, no atomics).  Index lists are padded to a multiple of 16 entries with valid
@@ -1736,15 +1689,12 @@ __global__ __launch_bounds__(256) void order_w_bf16_kernel(const uint16_t *__res
 constexpr int kAtgSuperMin = 4;                 // at least this many 32-row super-steps per workgroup
 constexpr int kAtgMaxWgs = 256;
 constexpr int kAtgDepth = 2;
-constexpr int kAtgBufBytes = 2 * 2 * 8 * 2 * kFragBytes;   // [operand][MFMA step][tile][split] = 64 KiB (h2)
-// SCH (SchemeK): 0 two scaled fp16 parts, two LDS buffers (one barrier per super-step); 1 three bf16
-// parts — the fp32-equivalent form, no bounds: its 96 KiB of fragments per super-step exist ONCE
-// (two buffers would not fit the LDS), so a second barrier separates multiply and publish.
-template <int SCH> constexpr int atg_buf_bytes() { return 2 * 2 * 8 * SchemeK<SCH>::NS * kFragBytes; }
-#ifndef ATG_B3_STEP16
-#define ATG_B3_STEP16 1
-#endif
-template <int SCH> constexpr int atg_lds_bytes() { return SCH == 0 ? 2 * atg_buf_bytes<SCH>() : (ATG_B3_STEP16 ? 3 * atg_buf_bytes<SCH>() / 2 : atg_buf_bytes<SCH>()); }
+// SCH (SchemeK): 0 two scaled fp16 parts, two LDS buffers of a super-step's fragments (one barrier per
+// super-step); 1 three bf16 parts — the fp32-equivalent form, no bounds: its 96 KiB of fragments per
+// super-step do not fit twice, so the LDS holds a ring of three 16-row step buffers (two barriers per
+// super-step, see the kernel).
+template <int SCH> constexpr int atg_buf_bytes() { return 2 * 2 * 8 * SchemeK<SCH>::NS * kFragBytes; }   // [operand][MFMA step][tile][split]
+template <int SCH> constexpr int atg_lds_bytes() { return SCH == 0 ? 2 * atg_buf_bytes<SCH>() : 3 * atg_buf_bytes<SCH>() / 2; }
 
 template <int SCH>
 __global__ __launch_bounds__(512, 2) void gemm_atg256_h2_kernel(
@@ -1755,7 +1705,7 @@ __global__ __launch_bounds__(512, 2) void gemm_atg256_h2_kernel(
 {
     // cs_partial (three-part ring form only, else NULL): [workgroups][256] column sums of the listed G rows —
     // the bias gradient of the layer whose weight gradient this is, from the rows the kernel loads anyway
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];       // 2 buffers of kAtgBufBytes
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];       // atg_lds_bytes<SCH>()
     const int tid = threadIdx.x, lane = tid & 63;
     [[maybe_unused]] unsigned long long st_begin = 0;
     GEMM_STAMP(st_begin);
@@ -1808,9 +1758,6 @@ __global__ __launch_bounds__(512, 2) void gemm_atg256_h2_kernel(
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = *(const f32x4 *)(src + (int64_t)idx[j] * ld);
     };
-#ifndef ATG_ABLATE      /* experiment builds only (tools/build_gemm_variants.sh atg): 4 = no loads in the loop */
-#define ATG_ABLATE 0
-#endif
     auto publish = [&](int64_t ss, f32x4 (&v)[8], unsigned char *buf) {
         // scale, zero the rows past the end of the list (and of the slab), split each column's 8
         // k-values into (h, m) fp16 parts: one 16-byte fragment per tile and split
@@ -1831,35 +1778,26 @@ __global__ __launch_bounds__(512, 2) void gemm_atg256_h2_kernel(
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             uint32_t hh[4], mm[4];
-            [[maybe_unused]] uint32_t ll[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                if constexpr (SCH == 1) {
-                    split3_pair(x[2 * j][q], x[2 * j + 1][q], hh[j], mm[j], ll[j]);
-                } else {
-                    f32x2 p = {x[2 * j][q], x[2 * j + 1][q]};
-                    const h16x2 ph = __builtin_convertvector(p, h16x2);
-                    const f32x2 pb = __builtin_convertvector(ph, f32x2);
-                    f32x2 r = {p.x - pb.x, p.y - pb.y};
-                    const h16x2 pm = __builtin_convertvector(r, h16x2);
-                    hh[j] = __builtin_bit_cast(uint32_t, ph);
-                    mm[j] = __builtin_bit_cast(uint32_t, pm);
-                }
+                f32x2 p = {x[2 * j][q], x[2 * j + 1][q]};
+                const h16x2 ph = __builtin_convertvector(p, h16x2);
+                const f32x2 pb = __builtin_convertvector(ph, f32x2);
+                f32x2 r = {p.x - pb.x, p.y - pb.y};
+                const h16x2 pm = __builtin_convertvector(r, h16x2);
+                hh[j] = __builtin_bit_cast(uint32_t, ph);
+                mm[j] = __builtin_bit_cast(uint32_t, pm);
             }
             unsigned char *tile = mine + (size_t)(2 * q) * NS * kFragBytes;      // tile 2q + (lane >> 5)
             *(u32x4 *)(tile) = u32x4{hh[0], hh[1], hh[2], hh[3]};
             *(u32x4 *)(tile + kFragBytes) = u32x4{mm[0], mm[1], mm[2], mm[3]};
-            if constexpr (SCH == 1) *(u32x4 *)(tile + 2 * kFragBytes) = u32x4{ll[0], ll[1], ll[2], ll[3]};
         }
     };
 
-#ifndef ATG_B3_STEP16     /* 0 (experiment builds): the three-part scheme on 32-row super-steps in ONE buffer, two barriers each */
-#define ATG_B3_STEP16 1
-#endif
-    if constexpr (SCH == 1 && ATG_B3_STEP16) {
-        // Three parts per operand: a 32-row super-step's fragments are 96 KiB, two of them do not fit the LDS,
-        // and in one buffer publish (270 vector instructions per wave: the split into three bf16 parts) and
-        // multiply (96 MFMAs) alternate between two barriers with the matrix pipe idle for 45 % of the cycles
+    if constexpr (SCH == 1) {
+        // Three parts per operand: a 32-row super-step's fragments are 96 KiB, two of them do not fit the LDS.
+        // In ONE buffer, publish (270 vector instructions per wave: the split into three bf16 parts) and
+        // multiply (96 MFMAs) alternated between two barriers with the matrix pipe idle for 45 % of the cycles
         // (stamps: 11 200 cycles per 32 rows against 6 144 of MFMA time; this form: 9 170 — and 7.25 -> 7.05 ms,
         // because the chip answers the denser pipe with a lower clock, 1.72 -> 1.59 GHz).  Here the unit of the LDS is ONE MFMA
         // step of 16 rows (48 KiB) in a ring of THREE: a super-step's two steps are multiplied one per barrier
@@ -1867,15 +1805,11 @@ __global__ __launch_bounds__(512, 2) void gemm_atg256_h2_kernel(
         // the two buffers that are free then — two pair splits (12 VALU each) behind every block of six MFMAs,
         // a tile's three fragment stores behind its fourth pair, fenced so that the order survives the
         // scheduler (hipcc, left alone, gathers the vector work in one place): it issues in the shadow of the
-        // wave's own MFMAs and of its SIMD partner's.  Same MFMA order over the rows: the same bits as the
-        // one-buffer form.  One code path for every wave and every super-step (a step past the slab publishes
+        // wave's own MFMAs and of its SIMD partner's.  Same MFMA order over the rows as the one-buffer form:
+        // the same bits.  One code path for every wave and every super-step (a step past the slab publishes
         // zeros into a free buffer): the accumulators never cross a branch.
         constexpr int kStepBytes = atg_buf_bytes<SCH>() / 2;            // [operand 2][tile 8][part 3][fragment]
-#ifndef ATG_B3_STAGGER    /* 1 (experiment builds): waves 4-7 split BEFORE a block's MFMAs, waves 0-3 behind them */
-#define ATG_B3_STAGGER 0
-#endif
         const int st_of = w8 >> 1, kh = w8 & 1;                          // this wave's rows: step of the super-step, k-half
-        const bool late = wave >= 4;                                      // (uniform) the SIMD partner of wave - 4
         const int64_t n_sup = s1 - s0;
         f32x4 v[8];
         auto fetch1 = [&](int64_t ss) {                        // loads only (rows of a super-step past the slab: its last)
@@ -1949,21 +1883,11 @@ __global__ __launch_bounds__(512, 2) void gemm_atg256_h2_kernel(
                 if (blk == 4) a_read(1);
                 if (blk + 1 < 8) b_read(blk + 1, Bf[(blk + 1) & 1]);
                 const u32x4 Bh = Bf[blk & 1][0], Bm = Bf[blk & 1][1], Bl = Bf[blk & 1][2];
-                // block b = 4 ib + jb: for tile q = b >> 1 the pairs (rows 2j, 2j + 1), j = 2 (b & 1), + 1.
-                // (STAGGER, measured and left off — 10 280 cycles per 32 rows against 9 170: waves 4-7 take a
-                //  block's vector work BEFORE its MFMAs, waves 0-3 after, so that SIMD partners alternate;
-                //  the branches are uniform and hold no accumulator)
+                // block b = 4 ib + jb: for tile q = b >> 1 the pairs (rows 2j, 2j + 1), j = 2 (b & 1), + 1,
+                // behind the block's MFMAs.  (Measured and dropped: waves 4-7 taking a block's vector work
+                // BEFORE its MFMAs, so that SIMD partners alternate — 10 280 cycles per 32 rows against 9 170.)
                 const int q = blk >> 1;
-                auto chunk = [&]() __attribute__((always_inline)) {
-                    pair_of(q, 2 * (blk & 1), k0, end, hh[2 * (blk & 1)], mm[2 * (blk & 1)], ll[2 * (blk & 1)]);
-                    pair_of(q, 2 * (blk & 1) + 1, k0, end, hh[2 * (blk & 1) + 1], mm[2 * (blk & 1) + 1], ll[2 * (blk & 1) + 1]);
-                    if (blk & 1) tile_store(dst + mine_off, q, hh, mm, ll);
-                };
-                if (publish) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (ATG_B3_STAGGER && late) chunk();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                if (publish) __builtin_amdgcn_sched_barrier(0);
                 f32x16 t = acc[ib][jb];
                 t = mfma(Af[0], Bl, t);        // smallest terms first
                 t = mfma(Af[2], Bh, t);
@@ -1974,7 +1898,9 @@ __global__ __launch_bounds__(512, 2) void gemm_atg256_h2_kernel(
                 acc[ib][jb] = t;
                 if (publish) {
                     __builtin_amdgcn_sched_barrier(0);
-                    if (!(ATG_B3_STAGGER && late)) chunk();
+                    pair_of(q, 2 * (blk & 1), k0, end, hh[2 * (blk & 1)], mm[2 * (blk & 1)], ll[2 * (blk & 1)]);
+                    pair_of(q, 2 * (blk & 1) + 1, k0, end, hh[2 * (blk & 1) + 1], mm[2 * (blk & 1) + 1], ll[2 * (blk & 1) + 1]);
+                    if (blk & 1) tile_store(dst + mine_off, q, hh, mm, ll);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -2003,8 +1929,7 @@ __global__ __launch_bounds__(512, 2) void gemm_atg256_h2_kernel(
             if (tid < 256)
                 cs_partial[(size_t)blockIdx.x * 256 + tid] = (red[tid] + red[256 + tid]) + (red[512 + tid] + red[768 + tid]);
         }
-    } else
-    if (s0 < s1) {                                               // (uniform over the workgroup)
+    } else if (s0 < s1) {                                        // (two parts; uniform over the workgroup)
 #pragma unroll
         for (int d = 0; d < kAtgDepth; ++d) {
             fetch(s0 + d, ring[d]);
@@ -2016,13 +1941,12 @@ __global__ __launch_bounds__(512, 2) void gemm_atg256_h2_kernel(
 #pragma unroll
             for (int d = 0; d < kAtgDepth; ++d) {
                 const int64_t ss = base + d;                     // (ss >= s1 in the last pass: zeros)
-                unsigned char *buf = lds + (SCH == 0 ? (int)((ss - s0) & 1) * atg_buf_bytes<SCH>() : 0);
+                unsigned char *buf = lds + (int)((ss - s0) & 1) * atg_buf_bytes<SCH>();
                 // (a scheduling fence: the arithmetic of THIS super-step's publish must not move up
                 //  into the previous one — it would wait there for loads that are one step younger)
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (SCH == 1) __syncthreads();     // (one buffer: everyone has multiplied the previous super-step)
                 publish(ss, ring[d], buf);
-                if (!(ATG_ABLATE & 4)) fetch(ss + kAtgDepth, ring[d]);
+                fetch(ss + kAtgDepth, ring[d]);
                 __syncthreads();
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
@@ -2039,23 +1963,12 @@ __global__ __launch_bounds__(512, 2) void gemm_atg256_h2_kernel(
                         const unsigned char *gb = gbase + ((4 * jh + jb) * NS) * kFragBytes;
                         const u32x4 Bh = *(const u32x4 *)(gb + (0 * 64 + lane) * 16);
                         const u32x4 Bm = *(const u32x4 *)(gb + (1 * 64 + lane) * 16);
-                        [[maybe_unused]] u32x4 Bl;
-                        if constexpr (SCH == 1) Bl = *(const u32x4 *)(gb + (2 * 64 + lane) * 16);
 #pragma unroll
                         for (int ib = 0; ib < 2; ++ib) {
                             f32x16 t = acc[ib][jb];
-                            if constexpr (SCH == 1) {          // smallest terms first
-                                t = mfma(Af[ib][0], Bl, t);
-                                t = mfma(Af[ib][2], Bh, t);
-                                t = mfma(Af[ib][1], Bm, t);
-                                t = mfma(Af[ib][0], Bm, t);
-                                t = mfma(Af[ib][1], Bh, t);
-                                t = mfma(Af[ib][0], Bh, t);
-                            } else {
-                                t = mfma_h(Af[ib][1], Bh, t);
-                                t = mfma_h(Af[ib][0], Bm, t);
-                                t = mfma_h(Af[ib][0], Bh, t);
-                            }
+                            t = mfma_h(Af[ib][1], Bh, t);       // smaller terms first
+                            t = mfma_h(Af[ib][0], Bm, t);
+                            t = mfma_h(Af[ib][0], Bh, t);
                             acc[ib][jb] = t;
                         }
                     }
@@ -2324,23 +2237,89 @@ size_t gcn_gemm_xw256_b3_workspace_bytes(void)
 
 }   // extern "C"
 
-// both decompositions of the 256 x 256 product (sch 0: two scaled fp16 parts, 1: three bf16 parts)
+namespace {
+
+// One launch of the 256-column product: the instantiation xw256_launch chose, and its arguments
+struct XwLaunch {
+    int form;       // 0 / 1: gemm_xw256_h2_kernel<epi, form> (two scaled fp16 / three bf16 parts), 2: gemm_xw256_s16_kernel
+    int epi;        // store section (the kernels' EPI)
+    bool bits;      // gemm_xw256_s16_kernel<epi, true>: + the result as keep bits
+    unsigned grid;
+    hipStream_t s;
+    const float *X;
+    int64_t ldx;
+    const int32_t *x_rows;
+    const unsigned char *ws;
+    const float *x_bound;
+    float *Y;
+    int64_t ldy, M;
+    uint32_t *y_absmax;
+    H2Epi ep;
+};
+
+// one instantiation: its kernel, its dynamic LDS (the W stages + every wave's X ring) and its launch
+template <int FORM, int EPI, bool BITS = false> struct Xw {
+    static constexpr int kLds = FORM == 2 ? kS16LdsBytes : kXLdsBytes;
+    static const void *kernel()
+    {
+        if constexpr (FORM == 2) return (const void *)gemm_xw256_s16_kernel<EPI, BITS>;
+        else return (const void *)gemm_xw256_h2_kernel<EPI, FORM>;
+    }
+    static bool launch(const XwLaunch &a)          // (false: `a` asks for another instantiation)
+    {
+        if (a.form != FORM || a.epi != EPI || a.bits != BITS) return false;
+        if constexpr (FORM == 2)
+            hipLaunchKernelGGL((gemm_xw256_s16_kernel<EPI, BITS>), dim3(a.grid), dim3(kThreads), kLds, a.s, a.X, a.ldx,
+                               a.ws, a.Y, a.ldy, a.M, a.y_absmax, a.ep);
+        else
+            hipLaunchKernelGGL((gemm_xw256_h2_kernel<EPI, FORM>), dim3(a.grid), dim3(kThreads), kLds, a.s, a.X, a.ldx,
+                               a.x_rows, a.ws, a.x_bound, a.Y, a.ldy, a.M, a.y_absmax, a.ep);
+        return true;
+    }
+};
+
+template <class... K> struct XwList {
+    static hipError_t set_lds()
+    {
+        hipError_t e = hipSuccess;
+        ((e = e != hipSuccess ? e : hipFuncSetAttribute(K::kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, K::kLds)),
+         ...);
+        return e;
+    }
+    static bool launch(const XwLaunch &a) { return (K::launch(a) || ...); }
+};
+
+// Every instantiation xw256_launch can choose, in ONE list: the LDS limits its first call raises and the
+// kernels a launch picks from are the same set.  (s16 has no EPI 6: sixteen Philox calls per tile keep hipcc
+// from unrolling its stages; EPI 3 and keep bits exist in its lane order only)
+using XwKernels = XwList<Xw<0, 0>, Xw<0, 1>, Xw<0, 2>, Xw<0, 4>, Xw<0, 5>, Xw<0, 6>,
+                         Xw<1, 0>, Xw<1, 1>, Xw<1, 2>, Xw<1, 4>, Xw<1, 5>, Xw<1, 6>,
+                         Xw<2, 0>, Xw<2, 1>, Xw<2, 2>, Xw<2, 3>, Xw<2, 4>, Xw<2, 5>, Xw<2, 4, true>, Xw<2, 5, true>>;
+
+}   // namespace
+
+// both decompositions of the 256 x 256 product (sch 0: two scaled fp16 parts, 1: three bf16 parts); every
+// error names `who`, the entry point that was called
 static int xw256_launch(const char *who, int sch, const float *X, int64_t ldx, const int32_t *x_rows, const float *W,
                         int64_t ldw, float *Y, int64_t ldy, int64_t M, const float *x_absmax_bound,
                         float *y_absmax, const gcn_gemm_epilogue *epi, void *workspace,
                         size_t workspace_bytes, void *stream)
 {
-    (void)who;
+    char msg[256];
+    auto named = [&](const char *what) -> const char * {
+        std::snprintf(msg, sizeof(msg), "%s%s", who, what);
+        return msg;
+    };
     const float *mask_src = epi ? epi->mask_src : nullptr;
     const int64_t ld_mask = epi ? epi->ld_mask : 0;
     H2Epi ep = {};
     if (epi != nullptr) {
         if (!(epi->dropout_p >= 0.f) || epi->dropout_p >= 1.f)
-            return gcn_internal_fail(GCN_E_BADARG, "gcn_gemm_xw256_f32_h2: dropout_p must be in [0, 1)");
+            return gcn_internal_fail(GCN_E_BADARG, named(": dropout_p must be in [0, 1)"));
         if (epi->dropout_p > 0.f && !epi->relu)
-            return gcn_internal_fail(GCN_E_BADARG, "gcn_gemm_xw256_f32_h2: dropout needs relu (out > 0 encodes the mask)");
+            return gcn_internal_fail(GCN_E_BADARG, named(": dropout needs relu (out > 0 encodes the mask)"));
         if ((mask_src != nullptr || epi->mask_bits != nullptr) && (epi->bias != nullptr || epi->relu || epi->dropout_p > 0.f))
-            return gcn_internal_fail(GCN_E_BADARG, "gcn_gemm_xw256_f32_h2: forward epilogue and backward mask exclude each other");
+            return gcn_internal_fail(GCN_E_BADARG, named(": forward epilogue and backward mask exclude each other"));
         ep.bias = epi->bias;
         ep.relu = epi->relu ? 1 : 0;
         ep.drop_thresh = gcn_dropout_threshold16(epi->dropout_p);
@@ -2357,38 +2336,37 @@ static int xw256_launch(const char *who, int sch, const float *X, int64_t ldx, c
         ep.mask_bits = epi->mask_bits;
     }
     if (M < 0 || ldx < kK || ldy < kN || ldw < kN)
-        return gcn_internal_fail(GCN_E_BADARG, "gcn_gemm_xw256_f32_h2: bad sizes");
+        return gcn_internal_fail(GCN_E_BADARG, named(": bad sizes"));
     if (M == 0) return 0;
     if (X == nullptr || W == nullptr || Y == nullptr || workspace == nullptr ||
         (sch == 0 && x_absmax_bound == nullptr))
-        return gcn_internal_fail(GCN_E_BADARG, "gcn_gemm_xw256_f32_h2: NULL pointer");
+        return gcn_internal_fail(GCN_E_BADARG, named(": NULL pointer"));
     if (workspace_bytes < (sch == 0 ? gcn_gemm_xw256_h2_workspace_bytes() : gcn_gemm_xw256_b3_workspace_bytes()))
-        return gcn_internal_fail(GCN_E_WORKSPACE, "gcn_gemm_xw256_f32_h2: workspace too small");
+        return gcn_internal_fail(GCN_E_WORKSPACE, named(": workspace too small"));
     if ((((uintptr_t)X) | ((uintptr_t)Y) | ((uintptr_t)workspace)) % 16 != 0 || (ldx % 4) != 0 ||
         (ldy % 4) != 0 || (((uintptr_t)x_absmax_bound) | ((uintptr_t)y_absmax)) % 4 != 0 ||
         ((uintptr_t)mask_src) % 16 != 0 || (mask_src != nullptr && (ld_mask % 4 != 0 || ld_mask < kN)) ||
         ((uintptr_t)ep.bias) % 16 != 0)
-        return gcn_internal_fail(GCN_E_ALIGN, "gcn_gemm_xw256_f32_h2: X / Y rows must be 16-byte aligned");
+        return gcn_internal_fail(GCN_E_ALIGN, named(": X / Y rows must be 16-byte aligned"));
     hipStream_t s = (hipStream_t)stream;
-#ifndef GEMM_B3_S16
-#define GEMM_B3_S16 1         /* 1: the three-part scheme on contiguous rows runs gemm_xw256_s16_kernel (128-row tiles, stores
-                                 under the next tile's MFMAs); 0: always gemm_xw256_h2_kernel<., 1> (bit-identical to round 1) */
-#endif
     // instantiation by store section (compile-time options, see the kernels): 0 plain, 2 backward mask,
-    // 1 bias, 4 bias + ReLU, 5 + dropout at p = 1/2 (one-bit keep fields), 6 + dropout at another p
+    // 3 backward mask from keep bits, 1 bias, 4 bias + ReLU, 5 + dropout at p = 1/2 (one-bit keep fields),
+    // 6 + dropout at another p
     const bool fwd = ep.bias != nullptr || ep.relu || ep.drop_thresh != 0u;
     const int variant = !fwd ? (ep.mask_bits != nullptr ? 3 : (ep.mask_src != nullptr ? 2 : 0))
                              : (!ep.relu ? 1 : (ep.drop_thresh == 0u ? 4 : (ep.drop_thresh == 32768u ? 5 : 6)));
-    // (s16 addresses a tile's rows as 32-bit offsets from the tile origin, takes no row list, and has no
-    //  instantiation for dropout at p != 1/2)
-    const bool s16 = sch == 1 && GEMM_B3_S16 && x_rows == nullptr && variant != 6 && ldx < (1 << 21) && ldy < (1 << 21);
+    // the three-part scheme on contiguous rows runs gemm_xw256_s16_kernel (128-row tiles, stores under the next
+    // tile's MFMAs).  (It addresses a tile's rows as 32-bit offsets from the tile origin, takes no row list, and
+    // has no instantiation for dropout at p != 1/2)
+    const bool s16 = sch == 1 && x_rows == nullptr && variant != 6 && ldx < (1 << 21) && ldy < (1 << 21);
     // (the one-bit mask exists in the contiguous-row kernel's lane order only: a launch that cannot take that kernel
     //  must be given mask_src / no keep_bits_out — refuse rather than ignore)
     if ((ep.mask_bits != nullptr || ep.keep_bits_out != nullptr) &&
         !(s16 && (ep.mask_bits != nullptr ? !fwd : (ep.relu != 0)) &&
           (((uintptr_t)ep.mask_bits) | ((uintptr_t)ep.keep_bits_out)) % 8 == 0))
-        return gcn_internal_fail(GCN_E_BADARG, "gcn_gemm_xw256_f32_b3: keep_bits_out / mask_bits need contiguous rows, the three-part "
-                                               "scheme, ReLU with dropout_p in {0, 1/2} (forward) or no forward epilogue (backward)");
+        return gcn_internal_fail(GCN_E_BADARG, named(": keep_bits_out / mask_bits need contiguous rows, the three-part "
+                                                     "scheme, ReLU with dropout_p in {0, 1/2} (forward) or no forward "
+                                                     "epilogue (backward)"));
     if (sch == 0)
         hipLaunchKernelGGL(split_w_h2_kernel, dim3(1), dim3(1024), 0, s, W, ldw, (unsigned char *)workspace);
     else if (s16)
@@ -2397,74 +2375,19 @@ static int xw256_launch(const char *who, int sch, const float *X, int64_t ldx, c
     else      // (the three-part image of gemm_xw256_kernel, behind the same header space)
         hipLaunchKernelGGL(split_w_kernel, dim3(kChunks * 8 * 64 / 256), dim3(256), 0, s, W, ldw,
                            (uint16_t *)((unsigned char *)workspace + kH2HeaderBytes));
+    static bool raised = false;          // (once, on the first call: a later one may be inside graph capture;
+    if (!raised) {                       //  idempotent, a benign race sets it twice)
+        const hipError_t ae = XwKernels::set_lds();
+        if (ae != hipSuccess) return gcn_internal_fail_hip((int)ae, named(": LDS size"));
+        raised = true;
+    }
     const int64_t tiles = s16 ? (M + kS16Rows - 1) / kS16Rows : (M + kTileRows - 1) / kTileRows;
-    // dynamic LDS of the X-through-LDS build: the two W stages + every wave's X ring (> 64 KiB)
-    const size_t dyn = s16 ? (size_t)kS16LdsBytes : (size_t)kXLdsBytes;
-    if (dyn) {
-        static bool raised = false;          // (idempotent; a benign race sets it twice)
-        if (!raised) {
-            const void *all[] = {(const void *)gemm_xw256_h2_kernel<0>, (const void *)gemm_xw256_h2_kernel<1>,
-                                 (const void *)gemm_xw256_h2_kernel<2>, (const void *)gemm_xw256_h2_kernel<4>,
-                                 (const void *)gemm_xw256_h2_kernel<5>, (const void *)gemm_xw256_h2_kernel<6>,
-                                 (const void *)gemm_xw256_h2_kernel<0, 1>, (const void *)gemm_xw256_h2_kernel<1, 1>,
-                                 (const void *)gemm_xw256_h2_kernel<2, 1>, (const void *)gemm_xw256_h2_kernel<4, 1>,
-                                 (const void *)gemm_xw256_h2_kernel<5, 1>, (const void *)gemm_xw256_h2_kernel<6, 1>};
-            for (const void *k : all) {
-                hipError_t ae = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kXLdsBytes);
-                if (ae != hipSuccess) return gcn_internal_fail_hip((int)ae, "gcn_gemm_xw256_f32_h2: LDS size");
-            }
-            const void *tall[] = {(const void *)gemm_xw256_s16_kernel<0>, (const void *)gemm_xw256_s16_kernel<1>,
-                                  (const void *)gemm_xw256_s16_kernel<2>, (const void *)gemm_xw256_s16_kernel<3>,
-                                  (const void *)gemm_xw256_s16_kernel<4>, (const void *)gemm_xw256_s16_kernel<5>,
-                                  (const void *)gemm_xw256_s16_kernel<4, true>, (const void *)gemm_xw256_s16_kernel<5, true>};
-            for (const void *k : tall) {
-                hipError_t ae = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kS16LdsBytes);
-                if (ae != hipSuccess) return gcn_internal_fail_hip((int)ae, "gcn_gemm_xw256_f32_b3: LDS size");
-            }
-            raised = true;
-        }
-    }
-    const unsigned grid = (fwd && !GEMM_H2_EPI_PERSIST) ? (unsigned)tiles : (unsigned)std::min<int64_t>(tiles, GEMM_H2_GRID);
-#define GCN_LAUNCH_H2(V)                                                                             \
-    do {                                                                                             \
-        if (sch == 0)                                                                                \
-            hipLaunchKernelGGL((gemm_xw256_h2_kernel<V, 0>), dim3(grid), dim3(kThreads), dyn, s, X, ldx, x_rows, \
-                               (const unsigned char *)workspace, x_absmax_bound, Y, ldy, M, (uint32_t *)y_absmax, ep); \
-        else if (s16)                                                                                \
-            hipLaunchKernelGGL((gemm_xw256_s16_kernel<(V == 6 ? 5 : V)>), dim3(grid), dim3(kThreads), dyn, s, X, ldx, \
-                               (const unsigned char *)workspace, Y, ldy, M, (uint32_t *)y_absmax, ep);     \
-        else                                                                                         \
-            hipLaunchKernelGGL((gemm_xw256_h2_kernel<V, 1>), dim3(grid), dim3(kThreads), dyn, s, X, ldx, x_rows, \
-                               (const unsigned char *)workspace, x_absmax_bound, Y, ldy, M, (uint32_t *)y_absmax, ep); \
-    } while (0)
-    switch (variant) {
-    case 0: GCN_LAUNCH_H2(0); break;
-    case 1: GCN_LAUNCH_H2(1); break;
-    case 2: GCN_LAUNCH_H2(2); break;
-    case 3:          // (s16 only: checked above)
-        hipLaunchKernelGGL((gemm_xw256_s16_kernel<3>), dim3(grid), dim3(kThreads), dyn, s, X, ldx,
-                           (const unsigned char *)workspace, Y, ldy, M, (uint32_t *)y_absmax, ep);
-        break;
-    case 4:
-    case 5:
-        if (s16 && ep.keep_bits_out != nullptr) {        // (+ the one-bit form of the result)
-            if (variant == 4)
-                hipLaunchKernelGGL((gemm_xw256_s16_kernel<4, true>), dim3(grid), dim3(kThreads), dyn, s, X, ldx,
-                                   (const unsigned char *)workspace, Y, ldy, M, (uint32_t *)y_absmax, ep);
-            else
-                hipLaunchKernelGGL((gemm_xw256_s16_kernel<5, true>), dim3(grid), dim3(kThreads), dyn, s, X, ldx,
-                                   (const unsigned char *)workspace, Y, ldy, M, (uint32_t *)y_absmax, ep);
-        } else if (variant == 4) {
-            GCN_LAUNCH_H2(4);
-        } else {
-            GCN_LAUNCH_H2(5);
-        }
-        break;
-    default: GCN_LAUNCH_H2(6); break;
-    }
-#undef GCN_LAUNCH_H2
+    const XwLaunch a = {s16 ? 2 : sch, variant, ep.keep_bits_out != nullptr && fwd,
+                        (unsigned)std::min<int64_t>(tiles, kXwGrid), s, X, ldx, x_rows,
+                        (const unsigned char *)workspace, x_absmax_bound, Y, ldy, M, (uint32_t *)y_absmax, ep};
+    if (!XwKernels::launch(a)) return gcn_internal_fail(GCN_E_BADARG, named(": no kernel for these options"));
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return gcn_internal_fail_hip((int)e, "gcn_gemm_xw256_f32_h2 launch");
+    if (e != hipSuccess) return gcn_internal_fail_hip((int)e, named(" launch"));
     return 0;
 }
 
@@ -2607,7 +2530,7 @@ static int atg256_launch(int sch, const float *A, int64_t lda, const int32_t *ro
     if (n_list < 0 || lda < kK || ldg < kN || ldo < kN)
         return gcn_internal_fail(GCN_E_BADARG, "gcn_gemm_atg256_f32: bad sizes");
     if (out == nullptr) return gcn_internal_fail(GCN_E_BADARG, "gcn_gemm_atg256_f32: NULL output");
-    if (colsum_g != nullptr && !(sch == 1 && ATG_B3_STEP16))
+    if (colsum_g != nullptr && sch != 1)
         return gcn_internal_fail(GCN_E_BADARG, "gcn_gemm_atg256_f32: column sums exist in the three-part form only");
     hipStream_t s = (hipStream_t)stream;
     if (n_list == 0) {

@@ -50,10 +50,7 @@ static inline float gcn_dropout_scale16(uint32_t thresh)
 namespace {
 
 constexpr int kWave = 64;
-#ifndef GCN_WPB
-#define GCN_WPB 4
-#endif
-constexpr int kWavesPerBlock = GCN_WPB;
+constexpr int kWavesPerBlock = 4;
 constexpr int kDefaultItemCost = GCN_DEFAULT_ITEM_COST;
 constexpr int kDefaultLongThresh = GCN_DEFAULT_LONG_THRESH;
 
@@ -369,11 +366,7 @@ __device__ __forceinline__ uint32_t store_out(const KParams &p, int64_t row, int
     }
     if (do_store) {
         T *dst = (T *)p.C + row * p.ldc + f;
-#if SPMM_STORE_NT
-        __builtin_nontemporal_store(Elem<T, VEC>::pack(o), (typename Elem<T, VEC>::Raw *)dst);
-#else
         *(typename Elem<T, VEC>::Raw *)dst = Elem<T, VEC>::pack(o);
-#endif
     }
     uint32_t amax = 0u;
     if (XEPI >= 2 && p.cabsmax != nullptr && do_store) {   // (uniform pointer test)
@@ -408,23 +401,14 @@ __device__ __forceinline__ void publish_absmax(const KParams &p, uint32_t amax)
 // scalars: base = B + col*ldb (SGPR pair), num_records = row bytes.  The hardware range check
 // returns zeros for lanes past the end of the row (feature tail) and for whole slots whose
 // num_records is 0 (slots past the end of an edge tile), so the gather needs no branches.
-#ifndef SPMM_GATHER_AUX    /* experiment builds (tools/build_spmm_variants.sh): cache policy of the gather */
-#define SPMM_GATHER_AUX 0  /* 0 default, 2 = nt (streaming) */
-#endif
-#ifndef SPMM_HUB_TAG       /* 1: bit 31 of a column index marks a HUB column — its row is loaded with the */
-#define SPMM_HUB_TAG 0     /*    default policy, every other row with SPMM_GATHER_AUX                     */
-#endif
-#ifndef SPMM_STORE_NT      /* 1: the result rows are stored non-temporally */
-#define SPMM_STORE_NT 0
-#endif
-template <int AUX = SPMM_GATHER_AUX>
+// (Default cache policy: non-temporal loads and stores were measured and dropped)
 __device__ __forceinline__ u32x4 row_load16(uint64_t base, uint32_t nbytes, uint32_t voff)
 {
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base);
     const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
     void *pb = (void *)(((uint64_t)hi << 32) | lo);
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(pb, 0, nbytes, 0x00020000);
-    return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, AUX);
+    return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0);
 }
 
 template <typename T, int VEC, int D, bool ROWS, bool FLAGS, int XEPI>
@@ -528,15 +512,8 @@ __device__ __forceinline__ void wide_stream(const KParams &p, const int32_t *__r
 #pragma unroll
             for (int j = 0; j < D; ++j) {
                 const bool ok = k + j < cnt;
-#if SPMM_HUB_TAG
-                const int ct = readlane_i(cv, k + j);
-                const int c = ct & 0x7fffffff;
-                if (ct < 0) x[j] = row_load16<0>(row_base(c), ok ? row_bytes : 0u, ld_off_bytes);
-                else x[j] = row_load16<SPMM_GATHER_AUX>(row_base(c), ok ? row_bytes : 0u, ld_off_bytes);
-#else
                 const int c = readlane_i(cv, k + j);   // k + j <= 63 always (k <= 56)
                 x[j] = row_load16(row_base(c), ok ? row_bytes : 0u, ld_off_bytes);
-#endif
             }
 #pragma unroll
             for (int j = 0; j < D; ++j)
@@ -786,18 +763,10 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void spmm_narrow_kernel(KPar
     // Row ends and the (col, val) tile of the item (<= 64 entries) sit in lanes and are read
     // with ds_bpermute: no dependent memory round trip per row.
     typedef typename Elem<T, VEC>::Raw Raw;
-#ifndef GCN_RU      // tuned on MI355X (C4 graph): RU 2 / UU 2 / kShort 8 beat 1,3,4 / 1,4 / 4,16,32
-#define GCN_RU 2
-#endif
-#ifndef GCN_UU
-#define GCN_UU 2
-#endif
-#ifndef GCN_KSHORT
-#define GCN_KSHORT 8
-#endif
-    constexpr int RU = GCN_RU;                // rounds in flight
-    constexpr int UU = GCN_UU;                // entries per row per step
-    constexpr int kShort = GCN_KSHORT;        // rows longer than this take the edge-split path
+    // (tuned on MI355X, C4 graph: RU 2 / UU 2 / kShort 8 beat 1,3,4 / 1,4 / 4,16,32)
+    constexpr int RU = 2;                     // rounds in flight
+    constexpr int UU = 2;                     // entries per row per step
+    constexpr int kShort = 8;                 // rows longer than this take the edge-split path
     const int64_t ldb_bytes = p.ldb * (int64_t)sizeof(T);
     int cv = 0;
     float vv = 0.f;
@@ -1027,10 +996,9 @@ __global__ __launch_bounds__(256) void bwd_colsum_kernel(const T *__restrict__ g
 #pragma unroll
     for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
     int nz_count = 0;
-#ifndef GCN_CS_UNROLL   // measured on MI355X: unroll 2 / 4 and 8192 slabs change nothing (+-1 %): the
-#define GCN_CS_UNROLL 1 // pass already runs at the device's mixed read+write rate, 5.5 TB/s
-#endif
-#pragma unroll GCN_CS_UNROLL
+    // (measured on MI355X: unroll 2 / 4 and 8192 slabs change nothing (+-1 %): the pass already runs at
+    //  the device's mixed read+write rate, 5.5 TB/s)
+#pragma unroll 1
     for (int64_t r = r0 + rl; r < r1; r += RL) {
         const int64_t off = r * F + VEC * cg;
         float g[VEC];
@@ -1628,10 +1596,7 @@ int gcn_relu_dropout_backward(int dtype, const void *grad_out, const void *out, 
     return 0;
 }
 
-#ifndef GCN_CS_BLOCKS
-#define GCN_CS_BLOCKS 2048
-#endif
-static constexpr int64_t kColsumBlocks = GCN_CS_BLOCKS;   // slabs of rows = partial column sums
+static constexpr int64_t kColsumBlocks = 2048;   // slabs of rows = partial column sums
 
 static bool colsum_shape_ok(int64_t F, int dtype)
 {

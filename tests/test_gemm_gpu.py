@@ -175,6 +175,11 @@ def test_gemm_declines_other_shapes(dev):
                       torch.randn(256, 256, device=dev).bfloat16()) is None
     odd = torch.randn(10, 257, device=dev)[:, 1:]            # rows start 4 bytes off a 16-byte boundary
     assert gemm_xw256(odd, torch.randn(256, 256, device=dev)) is None
+    from pygcn_amd import _native                            # (an error names the entry point that was called)
+    L, X = _native.lib(), torch.randn(10, 256, device=dev)
+    with pytest.raises(RuntimeError, match="gcn_gemm_xw256_f32_b3: bad sizes"):
+        _native.check(L.gcn_gemm_xw256_f32_b3(X.data_ptr(), 256, None, X.data_ptr(), 256, X.data_ptr(), 256, -1,
+                                              None, None, None, 0, None), "M = -1")
 
 
 def test_layer_256_to_256_through_custom_gemm(oracle, dev, gemm_scheme):
@@ -615,7 +620,7 @@ def test_bf16_gemm_mask_at_the_wider_shapes(dev, K, N):
 
 def test_dma_pipeline_is_deterministic_across_tiles_and_launches(dev, gemm_scheme):
     """The fp32 GEMM moves X and W by asynchronous HBM -> LDS DMA with hand-counted waits
-    (gcn_gemm.hip, GEMM_H2_XLDS): a wait that is one too weak would show as run-to-run noise.
+    (gcn_gemm.hip, dma16 / dma_wait): a wait that is one too weak would show as run-to-run noise.
     Many launches over inputs that give every persistent workgroup several tiles (cross-tile
     prefetch), a ragged last tile, a row list and both epilogues — all launches must store the same
     bits, and the plain result must match an fp64 product."""

@@ -76,7 +76,7 @@ def _popcount_rows(bits):
 
 def _pack_keep_bits(pos):
     """bool [m, 256] -> int32 [m, 8] in the lane order of gemm_xw256_s16_kernel's keep bits
-    (gcn_gemm.hip, `kb` / `bits_store`): lane q of a row writes words 2q, 2q + 1; bit 4·(cb & 7) + j of
+    (gcn_gemm.hip, `kb` / `write_keep_bits`): lane q of a row writes words 2q, 2q + 1; bit 4·(cb & 7) + j of
     word 2q + (cb >> 3) is column 16·cb + 4q + j (cb = 0..15, j = 0..3)."""
     w = torch.arange(8, device=pos.device).view(8, 1)
     b = torch.arange(32, device=pos.device).view(1, 32)
