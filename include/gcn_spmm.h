@@ -347,6 +347,9 @@ int gcn_csr_transpose_device(const void *rowptr, int rowptr_is64, const int32_t 
  *   GCN_REDUCE_SUM  what scipy's coo->csr conversion and torch.spmm on an uncoalesced tensor do;
  *   GCN_REDUCE_MAX  elementwise maximum — `adj + adj.T*(adj.T > adj) - adj*(adj.T > adj)`
  *                   (utils.py:365) is max(adj, adj.T), i.e. MAX over the entries of adj and adj.T.
+ * Non-finite duplicates stay in their own entry: under SUM a run holding inf sums to inf and a run
+ * holding a NaN (or both infinities) to NaN; MAX is fmaxf, which ignores a NaN member — the entry
+ * is NaN only if every member of its run is NaN.
  * Outputs: rowptr_out[n_rows+1] (int32 or int64), col_out / val_out with capacity nnz (sorted by
  * column inside every row), *nnz_out (DEVICE) = number of distinct entries.  All pointers DEVICE;
  * the caller guarantees 0 <= row < n_rows, 0 <= col < n_cols.  Deterministic, no atomics.
@@ -360,8 +363,11 @@ int gcn_coo_to_csr_device(const int64_t *row, const int64_t *col, const float *v
                           void *workspace, size_t workspace_bytes, void *stream);
 
 /*
- * val <- D^-1 · val in place on the DEVICE: every stored entry is divided by the sum of its row;
- * rows that sum to 0 stay 0.  The reference's `normalize(mx)` (pygcn/utils.py:390-397).
+ * val <- D^-1 · val in place on the DEVICE: every stored entry is multiplied by the reciprocal of
+ * the float32 sum of its row.  The reference's `normalize(mx)` (pygcn/utils.py:390-397), including
+ * its `r_inv[isinf(r_inv)] = 0`: a row whose reciprocal is infinite — a sum of exactly 0, or a
+ * subnormal sum below 2^-128 — becomes all zeros; so does a row whose sum overflows to +-inf (its
+ * reciprocal is 0); a row that holds a NaN becomes NaN, its neighbours are untouched.
  */
 int gcn_row_normalize_device(const void *rowptr, int rowptr_is64, float *val, int64_t n_rows,
                              void *stream);

@@ -88,8 +88,11 @@ __global__ __launch_bounds__(256) void unpack_entries_kernel(const uint64_t *__r
 }
 
 // D^-1 · M: one wavefront per row (grid-stride), lanes stride over the row's entries,
-// wavefront shuffle reduction of the row sum, then the scaling pass.  Rows that sum to 0 stay 0
-// (the reference turns the infinite reciprocal into 0: pygcn/utils.py:394).
+// wavefront shuffle reduction of the row sum, then the scaling pass.  A row whose float32 sum has
+// an INFINITE reciprocal becomes 0, as in the reference (`r_inv[np.isinf(r_inv)] = 0.`,
+// pygcn/utils.py:394): that is a sum of exactly 0 and also a subnormal sum below 2^-128 (float32
+// subnormals are not flushed here).  A sum that overflows to +-inf has the reciprocal 0 by itself;
+// a NaN in a row makes that row NaN — both as in the reference.
 template <typename IdxT>
 __global__ __launch_bounds__(256) void row_normalize_kernel(const IdxT *__restrict__ rowptr,
                                                             float *__restrict__ val, int64_t n_rows)
@@ -103,7 +106,8 @@ __global__ __launch_bounds__(256) void row_normalize_kernel(const IdxT *__restri
         for (int64_t e = e0 + lane; e < e1; e += 64) s += val[e];
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-        const float inv = (s != 0.f) ? 1.f / s : 0.f;
+        float inv = 1.f / s;
+        if (__builtin_isinf(inv)) inv = 0.f;
         for (int64_t e = e0 + lane; e < e1; e += 64) val[e] *= inv;
     }
 }
@@ -114,6 +118,9 @@ __global__ __launch_bounds__(256) void row_normalize_kernel(const IdxT *__restri
 // sequentially (sum: what scipy's coo->csr and torch.spmm on an uncoalesced COO tensor do; max: the
 // elementwise maximum the reference's symmetrization `adj + adj.T*(adj.T > adj) - adj*(adj.T > adj)`
 // amounts to), so the result does not depend on thread scheduling.  No atomics.
+// Non-finite members: under sum they propagate into their own entry only (inf, or NaN for
+// inf + -inf and for a NaN member); max is fmaxf, which IGNORES a NaN member — the entry is NaN only
+// if every member of its run is NaN (the reference's recipe only ever takes the maximum of counts).
 __global__ __launch_bounds__(256) void coo_keys_kernel(const int64_t *__restrict__ row,
                                                        const int64_t *__restrict__ col, int64_t nnz,
                                                        int64_t n_cols, uint64_t *__restrict__ key,

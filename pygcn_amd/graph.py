@@ -320,8 +320,9 @@ class CSRGraph:
 
     def row_normalize_(self):
         """In place D^-1 · A on the device (`gcn_row_normalize_device`): the reference's
-        `normalize(mx)` (pygcn/utils.py:390-397); rows that sum to 0 stay 0.  Invalidates the
-        cached transpose."""
+        `normalize(mx)` (pygcn/utils.py:390-397); rows whose sum has an infinite float32
+        reciprocal (0, or a subnormal below 2^-128) become 0, as there.  Invalidates the cached
+        transpose."""
         with torch.cuda.device(self.device):
             rc = _native.lib().gcn_row_normalize_device(
                 self.rowptr.data_ptr(), int(self.rowptr.dtype == torch.int64),

@@ -185,7 +185,31 @@ def g5_trajectory(adj_t, epochs=200):
     }
 
 
-def main():
+# ---------------------------------------------------------------- G6: normalize on hard rows
+def g6_normalize():
+    """The reference's two live ingest helpers on the seeded float32 matrix of
+    inputs.g6_normalize_input (rows that cancel, hold only zeros, sum to a subnormal, overflow,
+    hold a NaN; empty rows; a 300-entry row).  Only their outputs are stored: the values
+    `normalize` returns (CSR order) and the COO triplets `sparse_mx_to_torch_sparse_tensor` emits."""
+    rowptr, col, val, shape = gin.g6_normalize_input()
+    with np.errstate(all="ignore"):        # (the reference divides by the zero row sums on purpose)
+        mx = sp.csr_matrix(ref_utils.normalize(sp.csr_matrix((val, col, rowptr), shape=shape)))
+    assert mx.dtype == np.float32
+    t = ref_utils.sparse_mx_to_torch_sparse_tensor(mx)
+    return {"val": mx.data, "indptr": mx.indptr.astype(np.int32),
+            "coo_row": to_np(t._indices()[0]).astype(np.int32),
+            "coo_col": to_np(t._indices()[1]).astype(np.int32), "coo_val": to_np(t._values())}
+
+
+def main(only=()):
+    """Without arguments every fixture is rewritten; `make_golden.py g6` writes g6_normalize.npz
+    alone (the fixtures that exist stay byte-identical)."""
+    if only:
+        if set(only) != {"g6"}:
+            raise SystemExit("only g6 can be written on its own")
+        np.savez_compressed(os.path.join(HERE, "g6_normalize.npz"), **g6_normalize())
+        print("g6_normalize.npz", os.path.getsize(os.path.join(HERE, "g6_normalize.npz")))
+        return
     g1, gc1, gc2 = g1_init()
     np.savez_compressed(os.path.join(HERE, "g1_init.npz"), **g1)
 
@@ -207,6 +231,7 @@ def main():
     np.savez_compressed(os.path.join(HERE, "g3_generator_gcn.npz"), **g3_generator())
     np.savez_compressed(os.path.join(HERE, "g4_edge_cases.npz"), **g4_edge_cases())
     np.savez_compressed(os.path.join(HERE, "g5_trajectory.npz"), **g5_trajectory(adj_t))
+    np.savez_compressed(os.path.join(HERE, "g6_normalize.npz"), **g6_normalize())
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)))
@@ -214,4 +239,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])
