@@ -31,6 +31,13 @@ Only structurally-zero rows are skipped: the result is the same sum of the same 
 The forward pass is the ordinary one (both products over all rows, fused bias / ReLU / dropout /
 log_softmax epilogues): the full log-probability matrix exists and can be kept (`keep_full=True`)
 for validation on other rows, as upstream's --fastmode does.
+
+The backward pass is written ONCE, as two stages every route drives — `_loss_rows_stage` (grad_pre2
+and grad_b2) and `_hidden_layer_stage` (grad_W2, grad_pre1, grad_b1, grad_W1 from the saved Â·X) —
+with the route's own sparse product between them: `_gcn2_backward_rows` (the block of Âᵀ),
+`_gcn2_backward_dense` (the full CSR(Âᵀ), no row lists), the sharded pass of
+pygcn_amd/sharded_fused.py (the block plus a halo of gradient rows), and, for the first stage, the
+last-layer branch of `GraphConvFunction._backward_rows` (pygcn_amd/spmm.py).
 """
 import weakref
 
@@ -42,8 +49,22 @@ from .spmm import (_dense_forward, _weight_grad, gemm_xw256, log_softmax_fusable
                    spmm_csr)
 
 
-def _maybe_poisoned(shape, dtype, device):      # (reads the test switch at call time)
-    return _spmm._maybe_poisoned(shape, dtype, device)
+def _describe_rows(rs, rows):
+    """Fills what every row-set object says about the loss rows themselves (int64 `rows`, in the
+    user's order): rows_user, rows_u (sorted, unique), inverse, n_u, has_duplicates, sorted_unique."""
+    rs.rows_user = rows
+    rs.rows_u, rs.inverse = torch.unique(rows, return_inverse=True)             # sorted
+    rs.n_u = int(rs.rows_u.numel())
+    rs.has_duplicates = rs.n_u != rows.numel()
+    rs.sorted_unique = bool(not rs.has_duplicates and (rs.n_u == 0 or bool((rows == rs.rows_u).all())))
+
+
+def _list_rows2(rs, rows2):
+    """Fills the forms of R2 (sorted int64 `rows2`) the kernels read: rows2, n2, rows2_i32 (the
+    mask rows of the grad_input GEMM), rows2_padded (the weight-gradient kernel's list)."""
+    rs.rows2, rs.n2 = rows2, int(rows2.numel())
+    rs.rows2_i32 = rows2.to(torch.int32)
+    rs.rows2_padded = _spmm.padded_row_list(rows2)
 
 
 class RowSets:
@@ -57,18 +78,14 @@ class RowSets:
         rows = rows.to(device=dev, dtype=torch.int64)
         if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= n):
             raise RuntimeError("rows: index out of range")
-        self.rows_user = rows
-        self.rows_u, self.inverse = torch.unique(rows, return_inverse=True)      # sorted
-        self.has_duplicates = self.rows_u.numel() != rows.numel()
-        self.n_u = int(self.rows_u.numel())
+        _describe_rows(self, rows)
         rp = graph.rowptr.to(torch.int64)
         starts, lens = rp[self.rows_u], rp[self.rows_u + 1] - rp[self.rows_u]
         total = int(lens.sum())
         idx = torch.repeat_interleave(starts - torch.cumsum(lens, 0) + lens, lens) + \
             torch.arange(total, device=dev)
         cols = graph.col[idx].to(torch.int64)
-        self.rows2 = torch.unique(cols)                                          # sorted
-        self.n2 = int(self.rows2.numel())
+        _list_rows2(self, torch.unique(cols))                                     # sorted
         # The block of Âᵀ the backward product needs — rows R2, columns R — as its own small CSR
         # (compact row / column numbering): entry (r, c) of Â with r in R becomes entry
         # (pos of c in R2, pos of r in R) of the block.  Sorted by (row, source row): within a row
@@ -82,10 +99,6 @@ class RowSets:
         self.at_block = CSRGraph(rp.to(torch.int32 if total < 2 ** 31 - 1 else torch.int64),
                                  src[order].to(torch.int32), graph.val[idx][order].contiguous(),
                                  (self.n2, self.n_u))
-        self.sorted_unique = bool(self.n_u == rows.numel() and (self.n_u == 0 or bool(
-            (rows == self.rows_u).all())))
-        self.rows2_i32 = self.rows2.to(torch.int32)
-        self.rows2_padded = _spmm.padded_row_list(self.rows2)     # (for the weight-gradient kernel)
         mask2 = torch.zeros(graph.shape[1], dtype=torch.bool, device=dev)
         mask2[self.rows2] = True
         self.hint2 = pack_row_flags(mask2)
@@ -120,21 +133,12 @@ def fusable(model_dtype, nclass, graph, x):
             and log_softmax_fusable(nclass, model_dtype))
 
 
-def _rows_honoured(n, width, dtype, count):
-    """The device-side rule of the product (use_row_flags in gcn_spmm.hip, mirrored by
-    spmm._hint_will_be_used) for a freshly allocated [n, width] operand: rows whose hint bit is
-    clear are skipped below 3/4 non-zero rows in the wide kernel, below 1/8 in the narrow one."""
-    v = 16 // torch.empty((), dtype=dtype).element_size()
-    wide = width % v == 0 and width // v > 32
-    from . import tuning
-    return tuning.below(count, n, tuning.HINT_WIDE_MAX_SHARE if wide else tuning.HINT_NARROW_MAX_SHARE)
-
-
 def _operand_buffer(n, width, dtype, device, rows, values, count):
     """[n, width] tensor holding `values` at `rows`; the other rows are left UNWRITTEN when the
     product that reads it is certain to honour the row hint (it then never touches them), and are
     zero otherwise."""
-    buf = _maybe_poisoned((n, width), dtype, device) if _rows_honoured(n, width, dtype, count) \
+    honoured = _spmm._hint_will_be_used(n, width, torch.finfo(dtype).bits // 8, True, count)   # (fresh: aligned)
+    buf = _spmm._maybe_poisoned((n, width), dtype, device) if honoured \
         else torch.zeros((n, width), dtype=dtype, device=device)
     if rows is not None:           # (None: the caller writes the rows itself)
         buf.index_copy_(0, rows, values)
@@ -219,6 +223,122 @@ def _gcn2_forward(ctx, x, w1, b1, w2, b2, graph, dropout_p, seed):
     return (z if ctx.reassoc else x), h1, logp
 
 
+def _loss_rows_stage(grad, logp, want_colsum, rs=None, round_first=False):
+    """LOSS ROWS, the first stage of every one-node backward pass: log_softmax backward plus the
+    last layer's bias sums.  `grad` — a dense [m, C] tensor or an NLLGrad — is the gradient that
+    arrives for the log-probabilities `logp` [m, C]; `rs` (None at full height) says through
+    has_duplicates / sorted_unique / inverse / n_u whether those m rows repeat or are out of order.
+    One HIP pass where the shape allows (gcn_nll_log_softmax_backward_colsum for an NLLGrad,
+    gcn_log_softmax_backward_colsum else: grad_pre and the column sums together), torch ops
+    otherwise — class counts the kernels do not take, rows listed twice.
+    Returns (grad_pre2 in logp's dtype, rows sorted and unique; column sums of grad_pre2 for the
+    bias gradient — fp32, or already rounded to logp's dtype by the HIP pass — or None when not
+    wanted).  `round_first`: the torch form sums the ROUNDED grad_pre2 (the one-node-per-layer
+    route's order for bf16; the model-level routes sum before rounding)."""
+    from .functional import NLLGrad
+    dt = logp.dtype
+    one_pass = None
+    if isinstance(grad, NLLGrad):
+        one_pass = _spmm.nll_log_softmax_backward(logp, grad.target, grad.coef)
+        if one_pass is None:
+            grad = grad.dense()
+    if one_pass is None and rs is None:
+        grad = grad.to(dt)          # (full height: another dtype is cast; with rows it takes the torch form)
+    if one_pass is None and grad.dtype == dt and not (rs is not None and rs.has_duplicates):
+        one_pass = _spmm.backward_with_colsum(grad.contiguous(), logp, log_softmax=True)
+    if one_pass is not None:
+        gp, colsum = one_pass[0], (one_pass[1] if want_colsum else None)
+    else:
+        g = grad.float()
+        gp = g - logp.float().exp() * g.sum(1, keepdim=True)
+        if round_first:
+            gp = gp.to(dt)
+        colsum = gp.float().sum(0) if want_colsum else None
+    gp = gp.to(dt)
+    if rs is not None and rs.has_duplicates:           # the same vertex listed twice: add up
+        gp = torch.zeros((rs.n_u, gp.shape[1]), dtype=dt, device=gp.device).index_add_(0, rs.inverse, gp)
+    elif rs is not None and not rs.sorted_unique:      # rows of R in sorted order (the block's columns)
+        gp = torch.empty_like(gp).index_copy_(0, rs.inverse, gp)
+    return gp, colsum
+
+
+def _hidden_layer_stage(h1, w2, grad_sup2, gs_bound, z, need_w2, need_w1, b1_dtype, scale, h_bound,
+                        z_bound, keep_bits, rows=None, l1_follows_l2=False):
+    """HIDDEN LAYER, the stage after the route's own layer-2 sparse product: from grad_sup2 (and
+    `gs_bound`, its bound for the scaled GEMMs, or None)
+
+        grad_W2   = h1ᵀ · grad_sup2         gather-fused MFMA kernel (weight_grad_rows)
+        grad_pre1 = mask(grad_sup2 · W2ᵀ)   MFMA GEMM with the ReLU / dropout mask (h1 > 0, or its
+                                            one-bit form `keep_bits`) in its store
+        grad_b1, grad_W1 = zᵀ · grad_pre1   ONE pass over grad_pre1 where that kernel exists, else a
+                                            column-sum sweep and a second weight-gradient launch
+
+    `rows` names the rows of h1 / z that grad_sup2's rows stand for: an object with rows2 (int64),
+    rows2_i32, rows2_padded and n2 (RowSets, ShardedRowSets) — everything is then compact,
+    [n2, ·], and h1 / z are read in place through the lists — or None = all rows, in order (the
+    convention of weight_grad_rows' `rows_a` and gemm_xw256's `mask_rows`, which receive it as it
+    is).  `z` = Â·X saved by a reassociated first layer, or None: grad_W1 is then the caller's.
+    `b1_dtype`: dtype of the bias gradient, None when it is not wanted.  Shapes a kernel declines
+    fall through to the next form (each returns None before it allocates or launches).
+    `l1_follows_l2`: the full-height and the sharded pass reach for layer 1's gather-fused fp32
+    kernels only where layer 2's GEMMs were on theirs (256 classes too); the single-GPU row pass
+    asks the kernels alone.  The routes differ there (256 -> 256 -> C < 256), and each keeps its
+    launches.
+    Returns (grad_pre1, its bound or None, grad_W2, grad_b1, grad_W1)."""
+    dev, dt = h1.device, h1.dtype
+    f32 = dt == torch.float32
+    rows2, rows2_i32, rows2_padded, n2 = (rows.rows2, rows.rows2_i32, rows.rows2_padded, rows.n2) \
+        if rows is not None else (None,) * 4
+    if n2 == 0:          # an empty list (a rank without labelled neighbourhood): every sum is empty
+        def zeros(*shape, dtype=dt):
+            return torch.zeros(shape, dtype=dtype, device=dev)
+        return (zeros(0, h1.shape[1]), zeros(1, dtype=torch.float32) if f32 else None,
+                zeros(h1.shape[1], grad_sup2.shape[1]) if need_w2 else None,
+                zeros(h1.shape[1], dtype=b1_dtype) if b1_dtype is not None else None,
+                zeros(z.shape[1], h1.shape[1]) if (z is not None and need_w1) else None)
+    l2_fast = f32 and _spmm.gemm_handwritten() and grad_sup2.shape[1] == 256 and h1.shape[1] == 256
+    l1_kernels = l2_fast or not f32 or not l1_follows_l2
+    grad_w2 = grad_b1 = grad_w1 = h1c = None
+    if need_w2:
+        # (fp32 256 x 256, or bf16 128 x 128: rows of h1 read in place through the list)
+        grad_w2 = _spmm.weight_grad_rows(h1, grad_sup2, rows2_padded, None, h_bound, gs_bound, n_list=n2)
+        if grad_w2 is None:
+            h1c = h1 if rows2 is None else h1.index_select(0, rows2)
+            grad_w2 = _weight_grad(h1c, grad_sup2)
+    gh_max = torch.zeros(1, dtype=torch.float32, device=dev) if f32 else None
+    w2t = w2.t().contiguous()
+    gpre1 = gemm_xw256(grad_sup2, w2t, gs_bound, gh_max, mask_src=h1, mask_rows=rows2_i32,
+                       mask_bits=keep_bits, mask_scale=scale)
+    if gpre1 is None:                                  # (C5: the bf16 GEMM carries the mask in its store too)
+        gpre1 = _spmm.gemm_bf16(grad_sup2, w2t, mask_src=h1, mask_rows=rows2_i32, mask_scale=scale)
+    if gpre1 is None:
+        gh1 = _dense_forward(grad_sup2, w2t, gs_bound, gh_max)
+        if rows2 is None:
+            gpre1 = _spmm.relu_dropout_backward(gh1.contiguous(), h1, scale)
+        else:
+            h1c = h1.index_select(0, rows2) if h1c is None else h1c
+            gpre1 = torch.where(h1c > 0, gh1 * scale if scale != 1.0 else gh1,
+                                torch.zeros((), dtype=dt, device=dev))
+        if gh_max is not None:
+            gh_max = gh_max * scale
+        del gh1
+    del h1c
+    if b1_dtype is not None and z is not None and need_w1 and l1_kernels:
+        # grad_W1 and grad_b1 from ONE pass over grad_pre1: the weight-gradient kernel sums the rows it loads
+        both = _spmm.weight_grad_rows(z, gpre1, rows2_padded, None, z_bound, gh_max, n_list=n2, colsum_g=True)
+        if both is not None:
+            grad_w1, grad_b1 = both[0], both[1].to(b1_dtype)
+    if b1_dtype is not None and grad_b1 is None:
+        sums = _spmm.backward_with_colsum(gpre1) if gpre1.is_contiguous() else None   # (one HIP pass)
+        grad_b1 = (sums[1] if sums is not None else gpre1.float().sum(0)).to(b1_dtype)
+    if z is not None and need_w1 and grad_w1 is None:
+        if l1_kernels:
+            grad_w1 = _spmm.weight_grad_rows(z, gpre1, rows2_padded, None, z_bound, gh_max, n_list=n2)
+        if grad_w1 is None:
+            grad_w1 = _weight_grad(z if rows2 is None else z.index_select(0, rows2), gpre1)
+    return gpre1, gh_max, grad_w2, grad_b1, grad_w1
+
+
 def _gcn2_backward_rows(ctx, x, w1, w2, h1, out_rows, rs, grad_rows, needs):
     """Backward pass for a gradient that is non-zero on the loss rows only (module docstring):
     `grad_rows` [|rows|, C] in the user's row order, `out_rows` = logp at those rows.
@@ -227,22 +347,9 @@ def _gcn2_backward_rows(ctx, x, w1, w2, h1, out_rows, rs, grad_rows, needs):
     need_x, need_w1, need_b1, need_w2, need_b2 = needs
     n, dev, dt = graph.shape[0], x.device, h1.dtype
     graph_t = graph.t()
-    # ---- loss rows: log_softmax backward on the compact [|R|, C] tensors — one HIP pass
-    # (gcn_log_softmax_backward_colsum: grad_pre and the bias gradient's column sums together)
-    one_pass = _spmm.backward_with_colsum(grad_rows.contiguous(), out_rows, log_softmax=True) \
-        if (grad_rows.dtype == out_rows.dtype and not rs.has_duplicates) else None
-    if one_pass is not None:
-        gp, colsum, _ = one_pass
-        grad_b2 = colsum.to(ctx.bias_dtypes[1]) if (ctx.has_bias[1] and need_b2) else None
-    else:                                              # (class counts the kernel does not take)
-        g = grad_rows.float()
-        gp = g - out_rows.float().exp() * g.sum(1, keepdim=True)
-        grad_b2 = gp.sum(0).to(ctx.bias_dtypes[1]) if (ctx.has_bias[1] and need_b2) else None
-    gp = gp.to(dt)
-    if rs.has_duplicates:                              # the same vertex listed twice: add up
-        gp = torch.zeros((rs.n_u, gp.shape[1]), dtype=dt, device=dev).index_add_(0, rs.inverse, gp)
-    elif not rs.sorted_unique:                         # rows of R in sorted order (the block's columns)
-        gp = torch.empty_like(gp).index_copy_(0, rs.inverse, gp)
+    # ---- loss rows, compact [|R|, C]
+    gp, colsum = _loss_rows_stage(grad_rows, out_rows, ctx.has_bias[1] and need_b2, rs)
+    grad_b2 = colsum.to(ctx.bias_dtypes[1]) if colsum is not None else None
     grad_w1 = grad_w2 = grad_b1 = grad_x = None
     if not (need_x or need_w1 or need_b1 or need_w2):
         return grad_x, grad_w1, grad_b1, grad_w2, grad_b2
@@ -256,52 +363,14 @@ def _gcn2_backward_rows(ctx, x, w1, w2, h1, out_rows, rs, grad_rows, needs):
     gs_max = torch.zeros(1, dtype=torch.float32, device=dev) if f32 else None
     grad_sup2 = spmm_csr(rs.at_block, gp.contiguous(), tag="bwd_l2", c_absmax=gs_max)
     gs_bound = gs_max * 1.0001 if f32 else None
-    # h1 is read at the rows R2 in place (row lists), no compacting copy; the ReLU / dropout
-    # mask (h1 > 0 encodes ReLU and keep) is applied in the GEMM's store
-    fast = f32 and _spmm.gemm_handwritten() and grad_sup2.shape[1] == 256 and h1.shape[1] == 256
-    h1c = None
-    if need_w2:
-        # (fp32 256 x 256 with bounds, or bf16 128 x 128: rows of h1 read in place through the list)
-        grad_w2 = _spmm.weight_grad_rows(h1, grad_sup2, rs.rows2_padded, None,
-                                         ctx.h_bound, gs_bound, n_list=rs.n2) if (fast or not f32) else None
-        if grad_w2 is None:
-            h1c = h1.index_select(0, rs.rows2)
-            grad_w2 = _weight_grad(h1c, grad_sup2)
-    gh_max = torch.zeros(1, dtype=torch.float32, device=dev) if f32 else None
-    w2t = w2.t().contiguous()
-    gpre1 = gemm_xw256(grad_sup2, w2t, gs_bound, gh_max, mask_src=h1, mask_rows=rs.rows2_i32,
-                       mask_bits=getattr(ctx, "keep_bits", None),
-                       mask_scale=ctx.scale) if fast else None
-    if gpre1 is None and dt == torch.bfloat16:       # (C5: the bf16 GEMM carries the mask too)
-        gpre1 = _spmm.gemm_bf16(grad_sup2, w2t, mask_src=h1, mask_rows=rs.rows2_i32, mask_scale=ctx.scale)
-    if gpre1 is None:
-        h1c = h1.index_select(0, rs.rows2) if h1c is None else h1c
-        gh1 = _dense_forward(grad_sup2, w2t, gs_bound, gh_max)
-        gpre1 = torch.where(h1c > 0, gh1 * ctx.scale if ctx.scale != 1.0 else gh1,
-                            torch.zeros((), dtype=dt, device=dev))
-        if gh_max is not None:
-            gh_max = gh_max * ctx.scale
-        del gh1
-    del h1c, grad_sup2
-    gpre_bound = gh_max if f32 else None
-    want_b1 = ctx.has_bias[0] and need_b1
-    if want_b1 and ctx.reassoc and need_w1 and f32:
-        # grad_W1 and grad_b1 from ONE pass over grad_pre1: the weight-gradient kernel sums the rows it loads
-        both = _spmm.weight_grad_rows(x, gpre1, rs.rows2_padded, None, ctx.z_bound, gpre_bound, n_list=rs.n2,
-                                      colsum_g=True)
-        if both is not None:
-            grad_w1, grad_b1 = both[0], both[1].to(ctx.bias_dtypes[0])
-    if want_b1 and grad_b1 is None:
-        sums = _spmm.backward_with_colsum(gpre1) if gpre1.is_contiguous() else None   # (one HIP pass)
-        grad_b1 = (sums[1] if sums is not None else gpre1.float().sum(0)).to(ctx.bias_dtypes[0])
+    # ---- hidden layer, on the rows R2 (h1 and z read in place through the row lists)
+    gpre1, gpre_bound, grad_w2, grad_b1, grad_w1 = _hidden_layer_stage(
+        h1, w2, grad_sup2, gs_bound, x if ctx.reassoc else None, need_w2, need_w1,
+        ctx.bias_dtypes[0] if (ctx.has_bias[0] and need_b1) else None,
+        ctx.scale, ctx.h_bound, ctx.z_bound, ctx.keep_bits, rows=rs)
+    del grad_sup2
     # ---- layer 1
-    if ctx.reassoc:
-        z = x                                           # this step's Â·X, saved by forward
-        if need_w1 and grad_w1 is None:
-            grad_w1 = _spmm.weight_grad_rows(z, gpre1, rs.rows2_padded, None, ctx.z_bound,
-                                             gpre_bound, n_list=rs.n2)
-            if grad_w1 is None:
-                grad_w1 = _weight_grad(z.index_select(0, rs.rows2), gpre1)
+    if ctx.reassoc:                                     # (x is this step's Â·X, saved by forward)
         if need_x:                                      # grad_X = Âᵀ·(grad_pre1·W1ᵀ)
             gz = _dense_forward(gpre1, w1.t().contiguous(), gpre_bound)
             grad_z = _operand_buffer(n, gz.shape[1], dt, dev, rs.rows2, gz, rs.n2)
@@ -310,7 +379,7 @@ def _gcn2_backward_rows(ctx, x, w1, w2, h1, out_rows, rs, grad_rows, needs):
         if need_w1:
             # grad_W1 = (Â·X)[R2]ᵀ · grad_pre1[R2]: a forward product restricted to rows R2
             z = spmm_csr(graph, x, tag="bwd_l1", c_select=rs.hint2[0],
-                         out=_maybe_poisoned((n, x.shape[1]), x.dtype, dev))
+                         out=_spmm._maybe_poisoned((n, x.shape[1]), x.dtype, dev))
             if f32 and _spmm.gemm_handwritten() and x.shape[1] == 256 and gpre1.shape[1] == 256:
                 z_bound = graph.inf_norm() * ctx.x_bound * 1.0001 if ctx.x_bound is not None else None
                 grad_w1 = _spmm.weight_grad_rows(z, gpre1, rs.rows2_padded, None, z_bound,
@@ -333,38 +402,20 @@ def _gcn2_backward_dense(ctx, x, w1, w2, h1, logp, grad, needs):
     skipped, so the pass is the minimum number of full-height sweeps, each stage handing the next
     what it needs — no host synchronisation, no search for zero rows:
 
-        grad_pre2 (+ grad_b2)   log_softmax backward sweep; for the mean-NLL gradient (NLLGrad,
+        grad_pre2 (+ grad_b2)   _loss_rows_stage over all rows; for the mean-NLL gradient (NLLGrad,
                                 pygcn_amd/functional.py) the loss gradient is never materialised:
                                 coef·(onehot(target) − exp(logp)) straight from logp and the labels
         grad_sup2 = Âᵀ·grad_pre2        the SpMM kernel on CSR(Âᵀ), full height
-        grad_W2   = h1ᵀ·grad_sup2       gather-fused MFMA kernel (all rows, in order)
-        grad_pre1 = mask(grad_sup2·W2ᵀ) MFMA GEMM, ReLU / dropout mask (h1 > 0) in its store
-        grad_b1                         one column-sum sweep
-        grad_W1   = zᵀ·grad_pre1        with z = Â·X of the forward pass (layer 1 reassociated);
-                                        other shapes: Âᵀ·grad_pre1 first
+        grad_W2, grad_pre1, grad_b1     _hidden_layer_stage without row lists (all rows, in order)
+        grad_W1   = zᵀ·grad_pre1        there too, with z = Â·X of the forward pass (layer 1
+                                        reassociated); other shapes: Âᵀ·grad_pre1 first
     Returns (grad_x, grad_w1, grad_b1, grad_w2, grad_b2)."""
-    from .functional import NLLGrad
     graph = ctx.graph
     need_x, need_w1, need_b1, need_w2, need_b2 = needs
-    dev, dt = x.device, h1.dtype
-    f32 = dt == torch.float32
+    dev, f32 = x.device, h1.dtype == torch.float32
     graph_t = graph.t()
-    one_pass = None
-    if isinstance(grad, NLLGrad):
-        one_pass = _spmm.nll_log_softmax_backward(logp, grad.target, grad.coef)
-        if one_pass is None:
-            grad = grad.dense()
-    if one_pass is None:
-        grad = grad.to(logp.dtype).contiguous()
-        one_pass = _spmm.backward_with_colsum(grad, logp, log_softmax=True)
-    if one_pass is not None:
-        gp, colsum = one_pass[0], one_pass[1]
-        grad_b2 = colsum.to(ctx.bias_dtypes[1]) if (ctx.has_bias[1] and need_b2) else None
-    else:                                              # (class counts the kernel does not take)
-        g = grad.float()
-        gp = g - logp.float().exp() * g.sum(1, keepdim=True)
-        grad_b2 = gp.sum(0).to(ctx.bias_dtypes[1]) if (ctx.has_bias[1] and need_b2) else None
-        gp = gp.to(dt)
+    gp, colsum = _loss_rows_stage(grad, logp, ctx.has_bias[1] and need_b2)
+    grad_b2 = colsum.to(ctx.bias_dtypes[1]) if colsum is not None else None
     del grad
     grad_w1 = grad_w2 = grad_b1 = grad_x = None
     if not (need_x or need_w1 or need_b1 or need_w2):
@@ -376,41 +427,12 @@ def _gcn2_backward_dense(ctx, x, w1, w2, h1, logp, grad, needs):
     grad_sup2 = spmm_csr(graph_t, gp.contiguous(), tag="bwd_l2", c_absmax=gs_max)
     del gp
     gs_bound = gs_max * 1.0001 if f32 else None
-    fast = f32 and _spmm.gemm_handwritten() and grad_sup2.shape[1] == 256 and h1.shape[1] == 256
-    if need_w2:
-        grad_w2 = _spmm.weight_grad_rows(h1, grad_sup2, None, None, ctx.h_bound, gs_bound) \
-            if (fast or not f32) else None
-        if grad_w2 is None:
-            grad_w2 = _weight_grad(h1, grad_sup2)
-    gh_max = torch.zeros(1, dtype=torch.float32, device=dev) if f32 else None
-    w2t = w2.t().contiguous()
-    gpre1 = gemm_xw256(grad_sup2, w2t, gs_bound, gh_max, mask_src=h1, mask_scale=ctx.scale,
-                       mask_bits=getattr(ctx, "keep_bits", None)) if fast else None
-    if gpre1 is None and dt == torch.bfloat16:       # (C5: the bf16 GEMM carries the mask in its store too)
-        gpre1 = _spmm.gemm_bf16(grad_sup2, w2t, mask_src=h1, mask_scale=ctx.scale)
-    if gpre1 is None:
-        gh1 = _dense_forward(grad_sup2, w2t, gs_bound, gh_max)
-        gpre1 = _spmm.relu_dropout_backward(gh1.contiguous(), h1, ctx.scale)
-        if gh_max is not None:
-            gh_max = gh_max * ctx.scale
-        del gh1
+    gpre1, gpre_bound, grad_w2, grad_b1, grad_w1 = _hidden_layer_stage(
+        h1, w2, grad_sup2, gs_bound, x if ctx.reassoc else None, need_w2, need_w1,
+        ctx.bias_dtypes[0] if (ctx.has_bias[0] and need_b1) else None,
+        ctx.scale, ctx.h_bound, ctx.z_bound, ctx.keep_bits, l1_follows_l2=True)
     del grad_sup2
-    gpre_bound = gh_max if f32 else None
-    want_b1 = ctx.has_bias[0] and need_b1
-    if want_b1 and ctx.reassoc and need_w1 and fast and x.shape[1] == 256:
-        both = _spmm.weight_grad_rows(x, gpre1, None, None, ctx.z_bound, gpre_bound, colsum_g=True)   # (one pass for both)
-        if both is not None:
-            grad_w1, grad_b1 = both[0], both[1].to(ctx.bias_dtypes[0])
-    if want_b1 and grad_b1 is None:
-        sums = _spmm.backward_with_colsum(gpre1) if gpre1.is_contiguous() else None   # (one HIP pass)
-        grad_b1 = (sums[1] if sums is not None else gpre1.float().sum(0)).to(ctx.bias_dtypes[0])
     if ctx.reassoc:
-        z = x
-        if need_w1 and grad_w1 is None:
-            grad_w1 = _spmm.weight_grad_rows(z, gpre1, None, None, ctx.z_bound, gpre_bound) \
-                if ((fast and z.shape[1] == 256) or not f32) else None
-            if grad_w1 is None:
-                grad_w1 = _weight_grad(z, gpre1)
         if need_x:
             gz = _dense_forward(gpre1, w1.t().contiguous(), gpre_bound)
             grad_x = spmm_csr(graph_t, gz, tag="bwd_l1")

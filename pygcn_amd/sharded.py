@@ -58,8 +58,8 @@ import torch.distributed as dist
 
 from . import tuning
 from .graph import CSRGraph
-from .spmm import (_dense_forward, _grad_pre_and_bias, _weight_grad, dropout_scale, pack_row_flags, rows_pack,
-                   rows_unpack, spmm_csr, unpack_row_flags)
+from .spmm import (_dense_forward, _grad_pre_and_bias, _weight_grad, check_fused_epilogue, dropout_scale,
+                   pack_row_flags, rows_pack, rows_unpack, spmm_csr, unpack_row_flags)
 
 
 def partition_rows(rowptr, world):
@@ -813,16 +813,33 @@ def _check_static_rows(grad, flags):
                                "the rows declared by declare_loss_rows / declare_grad_rows")
 
 
+def _grad_exchange_args(sg, grad, hint, last_layer):
+    """What `sg.product(grad, transpose=True, ...)` is told about the zero rows of a layer's gradient
+    `grad` (contiguous; `hint` = the row bitmap of the fused backward pass, or None): the keyword
+    arguments row_nonzero / own_flags / static_key, empty with the row-sparse exchange switched off."""
+    if not sg.sparse_grad_exchange:
+        return {}
+    static_key = None
+    if last_layer and sg.static_grad_rows is not None:
+        # the loss rows were declared (declare_grad_rows): a structural row set — the
+        # count exchange ran once, this step synchronises with nobody
+        flags, static_key = sg.static_grad_rows, ("loss rows", sg._grad_rows_version)
+        _check_static_rows(grad, flags)
+    else:
+        # gradients of a loss on few labelled vertices: most rows are zero and need not
+        # travel.  The fused backward pass already produced the row bitmap; without it
+        # (shapes outside that kernel) the flags are computed here
+        flags = unpack_row_flags(hint[0], grad.shape[0]) if hint is not None else (grad != 0).any(1)
+    return {"row_nonzero": lambda idx: flags[idx], "own_flags": flags, "static_key": static_key}
+
+
 class ShardedSpMMFunction(torch.autograd.Function):
     """out_r = Â_r · allgather(support);  grad_support_r = (Âᵀ)_r · allgather(grad_out)."""
 
     @staticmethod
     def forward(ctx, sg, support_local, bias, relu=False, dropout_p=0.0, seed=0, log_softmax=False,
                 last_layer=False):
-        if dropout_p > 0.0 and not relu:
-            raise RuntimeError("fused dropout needs the fused ReLU (out > 0 encodes the mask)")
-        if log_softmax and relu:
-            raise RuntimeError("log_softmax cannot be combined with the fused ReLU / dropout")
+        check_fused_epilogue(relu, dropout_p, log_softmax)
         ctx.sg = sg
         ctx.last_layer = bool(last_layer or log_softmax)
         ctx.has_bias = bias is not None
@@ -846,24 +863,8 @@ class ShardedSpMMFunction(torch.autograd.Function):
                                             **({"log_softmax": True} if ctx.log_softmax else {}))
         if ctx.needs_input_grad[1]:
             grad_out = grad_out.contiguous()
-            row_nonzero = flags = static_key = None
-            if sg.sparse_grad_exchange:
-                if ctx.last_layer and sg.static_grad_rows is not None:
-                    # the loss rows were declared (declare_grad_rows): a structural row set — the
-                    # count exchange ran once, this step synchronises with nobody
-                    flags = sg.static_grad_rows
-                    static_key = ("loss rows", sg._grad_rows_version)
-                    _check_static_rows(grad_out, flags)
-                else:
-                    # gradients of a loss on few labelled vertices: most rows are zero and need not
-                    # travel.  The fused backward pass already produced the row bitmap; without it
-                    # (shapes outside that kernel) the flags are computed here
-                    flags = unpack_row_flags(hint[0], grad_out.shape[0]) if hint is not None else \
-                        (grad_out != 0).any(1)
-                row_nonzero = lambda idx: flags[idx]
-            grad_support = sg.product(grad_out, transpose=True, row_nonzero=row_nonzero,
-                                      own_flags=flags if row_nonzero is not None else None,
-                                      static_key=static_key)
+            grad_support = sg.product(grad_out, transpose=True,
+                                      **_grad_exchange_args(sg, grad_out, hint, ctx.last_layer))
         return None, grad_support, grad_bias, None, None, None, None, None
 
 
@@ -881,8 +882,7 @@ class ShardedHiddenLayerFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, sg, h_local, weight, bias, relu=False, dropout_p=0.0, seed=0, log_softmax=False,
                 last_layer=False):
-        if dropout_p > 0.0 and not relu:
-            raise RuntimeError("fused dropout needs the fused ReLU (out > 0 encodes the mask)")
+        check_fused_epilogue(relu, dropout_p)
         ctx.sg = sg
         ctx.has_bias = bias is not None
         ctx.relu, ctx.log_softmax = bool(relu), bool(log_softmax)
@@ -907,18 +907,8 @@ class ShardedHiddenLayerFunction(torch.autograd.Function):
         grad_h = grad_w = None
         if need_h or need_w:
             grad_pre = grad_pre.contiguous()
-            row_nonzero = flags = static_key = None
-            if sg.sparse_grad_exchange:
-                if ctx.last_layer and sg.static_grad_rows is not None:
-                    flags, static_key = sg.static_grad_rows, ("loss rows", sg._grad_rows_version)
-                    _check_static_rows(grad_pre, flags)
-                else:
-                    flags = unpack_row_flags(hint[0], grad_pre.shape[0]) if hint is not None else \
-                        (grad_pre != 0).any(1)
-                row_nonzero = lambda idx: flags[idx]
-            grad_support = sg.product(grad_pre, transpose=True, row_nonzero=row_nonzero,
-                                      own_flags=flags if row_nonzero is not None else None,
-                                      static_key=static_key)
+            grad_support = sg.product(grad_pre, transpose=True,
+                                      **_grad_exchange_args(sg, grad_pre, hint, ctx.last_layer))
             grad_h, grad_w = _dense_grads(h_local, weight, grad_support, need_h, need_w)
         return None, grad_h, grad_w, grad_bias, None, None, None, None, None
 
@@ -936,8 +926,7 @@ class ShardedInputLayerFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, sg, x_local, x_halo, weight, bias, relu=False, dropout_p=0.0, seed=0):
-        if dropout_p > 0.0 and not relu:
-            raise RuntimeError("fused dropout needs the fused ReLU (out > 0 encodes the mask)")
+        check_fused_epilogue(relu, dropout_p)
         ctx.sg = sg
         ctx.has_bias = bias is not None
         ctx.relu = bool(relu)

@@ -10,7 +10,8 @@ can be non-zero follows from the graph and R = ∪ R_r alone, so it is worked ou
     grad_sup2 = (Âᵀ)_r · grad_pre2                 this rank's rows R2_r = its vertices with a neighbour in R;
                                                    needs the rows of grad_pre2 in R that other ranks own
                                                    and this block references: a STATIC halo of gradient rows
-    everything after that is local and runs on the compact rows R2_r, as in fused.py
+    everything after that is local and runs on the compact rows R2_r: the two stages of fused.py
+    (`_loss_rows_stage` before the exchange, `_hidden_layer_stage` after the block product)
 
 Setup (collective): the ranks all-gather their R_r, each cuts the [R2_r, R] block of its rows of Âᵀ,
 and a HaloExchange over that block's columns fixes who sends which gradient rows to whom.  Per epoch
@@ -24,8 +25,9 @@ import torch
 import torch.distributed as dist
 
 from . import spmm as _spmm
+from .fused import _hidden_layer_stage, _loss_rows_stage, _describe_rows, _list_rows2
 from .sharded import HaloExchange
-from .spmm import _dense_forward, _weight_grad, gemm_xw256, log_softmax_fusable
+from .spmm import _dense_forward, log_softmax_fusable
 
 
 class ShardedRowSets:
@@ -37,11 +39,7 @@ class ShardedRowSets:
         rows = rows_local.to(torch.int64)
         if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= n_loc):
             raise RuntimeError("rows: index out of range of this rank's block")
-        self.rows_user = rows
-        self.rows_u, self.inverse = torch.unique(rows, return_inverse=True)          # sorted
-        self.n_u = int(self.rows_u.numel())
-        self.has_duplicates = self.n_u != rows.numel()
-        self.sorted_unique = bool(not self.has_duplicates and (self.n_u == 0 or bool((rows == self.rows_u).all())))
+        _describe_rows(self, rows)
         # R as global ids on every rank (rank blocks ascend, each part sorted: the whole is sorted)
         W = sg.world
         counts = torch.empty(W, dtype=torch.int64, device=dev)
@@ -68,10 +66,7 @@ class ShardedRowSets:
         erow = torch.repeat_interleave(torch.arange(n_loc, device=dev, dtype=torch.int64), deg)[keep]
         ecol, eval_ = col_g[keep], val[keep]
         del col, col_g, pos, keep
-        self.rows2 = torch.unique(erow)                                              # sorted local row ids
-        self.n2 = int(self.rows2.numel())
-        self.rows2_i32 = self.rows2.to(torch.int32)
-        self.rows2_padded = _spmm.padded_row_list(self.rows2)
+        _list_rows2(self, torch.unique(erow))                                         # sorted local row ids
         # who sends which rows of grad_pre2 to whom: a halo exchange over the block's columns
         self.hx = HaloExchange(ecol, sg.bounds, sg.rank, W, sg.group)                # (collective)
         own = self.hx.is_own
@@ -149,20 +144,9 @@ class ShardedGCN2RowsFunction(torch.autograd.Function):
         sg, rs = ctx.sg, ctx.rs
         need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[4:8]
         dev, dt = z.device, h1.dtype
-        one_pass = _spmm.backward_with_colsum(grad_rows.contiguous(), out_rows, log_softmax=True) \
-            if (grad_rows.dtype == out_rows.dtype and not rs.has_duplicates and rs.n_u) else None
-        if one_pass is not None:
-            gp, colsum, _ = one_pass
-            grad_b2 = colsum.to(ctx.bias_dtypes[1]) if (ctx.has_bias[1] and need_b2) else None
-        else:
-            g = grad_rows.float()
-            gp = g - out_rows.float().exp() * g.sum(1, keepdim=True)
-            grad_b2 = gp.sum(0).to(ctx.bias_dtypes[1]) if (ctx.has_bias[1] and need_b2) else None
-        gp = gp.to(dt)
-        if rs.has_duplicates:
-            gp = torch.zeros((rs.n_u, gp.shape[1]), dtype=dt, device=dev).index_add_(0, rs.inverse, gp)
-        elif not rs.sorted_unique:
-            gp = torch.empty_like(gp).index_copy_(0, rs.inverse, gp)
+        # ---- loss rows (fused._loss_rows_stage), compact [|R_r|, C]
+        gp, colsum = _loss_rows_stage(grad_rows, out_rows, ctx.has_bias[1] and need_b2, rs)
+        grad_b2 = colsum.to(ctx.bias_dtypes[1]) if colsum is not None else None
         gp = gp.contiguous()
         # ---- layer 2: the static halo of gradient rows, then the block product (compact in / out)
         ev = sg._tic(gp)
@@ -186,42 +170,9 @@ class ShardedGCN2RowsFunction(torch.autograd.Function):
             gs_bound = gs_max * 1.0001 if gs_max is not None else (
                 torch.linalg.vector_norm(grad_sup2, ord=float("inf")).float().reshape(1) * 1.0001
                 if rs.n2 else grad_sup2.new_zeros(1).float())
-        fast = f32 and _spmm.gemm_handwritten() and grad_sup2.shape[1] == 256 and h1.shape[1] == 256 \
-            and rs.n2 > 0
-        grad_w1 = grad_w2 = grad_b1 = None
-        h1c = None
-        if need_w2:
-            grad_w2 = _spmm.weight_grad_rows(h1, grad_sup2, rs.rows2_padded, None, ctx.h_bound, gs_bound,
-                                             n_list=rs.n2) if (fast or (not f32 and rs.n2 > 0)) else None
-            if grad_w2 is None:
-                h1c = h1.index_select(0, rs.rows2)
-                grad_w2 = _weight_grad(h1c, grad_sup2)
-        gh_max = torch.zeros(1, dtype=torch.float32, device=dev) if f32 else None
-        w2t = w2.t().contiguous()
-        gpre1 = gemm_xw256(grad_sup2, w2t, gs_bound, gh_max, mask_src=h1, mask_rows=rs.rows2_i32,
-                           mask_bits=getattr(ctx, "keep_bits", None), mask_scale=ctx.scale) if fast else None
-        if gpre1 is None and dt == torch.bfloat16 and rs.n2:
-            gpre1 = _spmm.gemm_bf16(grad_sup2, w2t, mask_src=h1, mask_rows=rs.rows2_i32, mask_scale=ctx.scale)
-        if gpre1 is None:
-            h1c = h1.index_select(0, rs.rows2) if h1c is None else h1c
-            gh1 = _dense_forward(grad_sup2, w2t, gs_bound, gh_max) if rs.n2 else grad_sup2.new_zeros((0, w2.shape[0]))
-            gpre1 = torch.where(h1c > 0, gh1 * ctx.scale if ctx.scale != 1.0 else gh1,
-                                torch.zeros((), dtype=dt, device=dev))
-            if gh_max is not None:
-                gh_max = gh_max * ctx.scale
-        want_b1 = ctx.has_bias[0] and need_b1
-        if want_b1 and need_w1 and fast and rs.n2 > 0:          # (grad_W1 and grad_b1 from one pass over grad_pre1)
-            both = _spmm.weight_grad_rows(z, gpre1, rs.rows2_padded, None, ctx.z_bound, gh_max if f32 else None,
-                                          n_list=rs.n2, colsum_g=True)
-            if both is not None:
-                grad_w1, grad_b1 = both[0], both[1].to(ctx.bias_dtypes[0])
-        if want_b1 and grad_b1 is None:
-            sums = _spmm.backward_with_colsum(gpre1) if (gpre1.is_contiguous() and rs.n2) else None
-            grad_b1 = (sums[1] if sums is not None else gpre1.float().sum(0)).to(ctx.bias_dtypes[0])
-        if need_w1 and grad_w1 is None:
-            grad_w1 = _spmm.weight_grad_rows(z, gpre1, rs.rows2_padded, None, ctx.z_bound,
-                                             gh_max if f32 else None, n_list=rs.n2) \
-                if (fast or (not f32 and rs.n2 > 0)) else None
-            if grad_w1 is None:
-                grad_w1 = _weight_grad(z.index_select(0, rs.rows2), gpre1)
+        # ---- hidden layer on the rows R2_r (fused._hidden_layer_stage; an empty R2_r is its business)
+        _, _, grad_w2, grad_b1, grad_w1 = _hidden_layer_stage(
+            h1, w2, grad_sup2, gs_bound, z, need_w2, need_w1,
+            ctx.bias_dtypes[0] if (ctx.has_bias[0] and need_b1) else None,
+            ctx.scale, ctx.h_bound, ctx.z_bound, ctx.keep_bits, rows=rs, l1_follows_l2=True)
         return None, None, None, None, grad_w1, grad_b1, grad_w2, grad_b2, None, None

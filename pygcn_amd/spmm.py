@@ -441,6 +441,14 @@ def dropout_seed_for(tensor):
     return t
 
 
+def check_fused_epilogue(relu, dropout_p, log_softmax=False):
+    """The argument rules of the fused epilogues, for every layer function's forward."""
+    if dropout_p > 0.0 and not relu:
+        raise RuntimeError("fused dropout needs the fused ReLU (out > 0 encodes the mask)")
+    if log_softmax and relu:
+        raise RuntimeError("log_softmax cannot be combined with the fused ReLU / dropout")
+
+
 class SpMMFunction(torch.autograd.Function):
     """out = dropout(relu(A · B + bias)) with every stage optional and fused into the kernel's
     store;  grad_B = A^T · grad_pre;  grad_bias = column sums of grad_pre, where
@@ -451,8 +459,7 @@ class SpMMFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, graph, B, bias, relu=False, dropout_p=0.0, seed=0):
-        if dropout_p > 0.0 and not relu:
-            raise RuntimeError("fused dropout needs the fused ReLU (out > 0 encodes the mask)")
+        check_fused_epilogue(relu, dropout_p)
         ctx.graph = graph
         ctx.has_bias = bias is not None
         ctx.relu = bool(relu)
@@ -998,14 +1005,13 @@ def set_row_compaction(enabled):
     _row_compaction = bool(enabled)
 
 
-def _hint_will_be_used(B, nz_rows):
-    """Mirror of the device-side rule (use_row_flags in gcn_spmm.hip): the product skips the
-    flagged-zero rows of its dense operand B below 3/4 non-zero rows in the wide kernel (16-byte
-    lanes, more than 32 of them per row) and below 1/8 in the narrow one."""
-    n, F = B.shape
-    v = 16 // B.element_size()
-    wide = (F % v == 0 and F // v > 32 and B.stride(1) == 1 and B.data_ptr() % 16 == 0
-            and (B.stride(0) * B.element_size()) % 16 == 0)
+def _hint_will_be_used(n, F, element_size, aligned, nz_rows):
+    """THE host mirror of the device-side rule (use_row_flags in gcn_spmm.hip): the product skips the
+    flagged-zero rows of its dense operand [n, F] below 3/4 non-zero rows in the wide kernel (16-byte
+    lanes, more than 32 of them per row; `aligned`: unit column stride, base and row pitch multiples
+    of 16 bytes) and below 1/8 in the narrow one."""
+    v = 16 // element_size
+    wide = aligned and F % v == 0 and F // v > 32
     return tuning.below(nz_rows, n, tuning.HINT_WIDE_MAX_SHARE if wide else tuning.HINT_NARROW_MAX_SHARE)
 
 
@@ -1026,10 +1032,7 @@ class GraphConvFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, input, weight, bias, graph, relu=False, dropout_p=0.0, seed=0,
                 log_softmax=False):
-        if dropout_p > 0.0 and not relu:
-            raise RuntimeError("fused dropout needs the fused ReLU (out > 0 encodes the mask)")
-        if log_softmax and relu:
-            raise RuntimeError("log_softmax cannot be combined with the fused ReLU / dropout")
+        check_fused_epilogue(relu, dropout_p, log_softmax)
         ctx.graph = graph
         ctx.relu = bool(relu)
         ctx.log_softmax = bool(log_softmax)
@@ -1091,22 +1094,12 @@ class GraphConvFunction(torch.autograd.Function):
         dev, dt = vals.device, vals.dtype
         f32 = dt == torch.float32
         if ctx.log_softmax:
-            # ---- last layer: log_softmax backward on the compact rows, then Âᵀ on its block
+            # ---- last layer: log_softmax backward on the compact rows (the loss-rows stage of fused.py; this
+            # route's torch form sums the bias gradient AFTER rounding to bf16), then Âᵀ on its block
             rs = fused.row_sets(graph, rows)
             out_rows = out.index_select(0, rs.rows_user)
-            one_pass = backward_with_colsum(vals.contiguous(), out_rows, log_softmax=True) \
-                if not rs.has_duplicates else None
-            if one_pass is not None:
-                gp, colsum, _ = one_pass
-                grad_bias = colsum if need_b else None
-            else:
-                g32 = vals.float()
-                gp = (g32 - out_rows.float().exp() * g32.sum(1, keepdim=True)).to(dt)
-                grad_bias = gp.float().sum(0).to(dt) if need_b else None
-            if rs.has_duplicates:
-                gp = torch.zeros((rs.n_u, gp.shape[1]), dtype=dt, device=dev).index_add_(0, rs.inverse, gp)
-            elif not rs.sorted_unique:
-                gp = torch.empty_like(gp).index_copy_(0, rs.inverse, gp)
+            gp, colsum = fused._loss_rows_stage(vals, out_rows, need_b, rs, round_first=True)
+            grad_bias = colsum.to(dt) if need_b else None
             if not (need_in or need_w):
                 return None, None, grad_bias, None, None, None, None, None
             grad_sup = spmm_csr(rs.at_block, gp.contiguous(), tag="bwd")          # [|R2|, Fout], compact
@@ -1222,7 +1215,9 @@ class GraphConvFunction(torch.autograd.Function):
             rows = torch.nonzero(unpack_row_flags(hint[0], grad_pre.shape[0])).squeeze(1)
             grad_w = _weight_grad(z.index_select(0, rows), grad_pre.index_select(0, rows))
             return None, grad_w, grad_bias, None, None, None, None, None
-        if unwritten and not _hint_will_be_used(grad_pre, nz_rows):
+        es = grad_pre.element_size()
+        aligned = grad_pre.stride(1) == 1 and grad_pre.data_ptr() % 16 == 0 and (grad_pre.stride(0) * es) % 16 == 0
+        if unwritten and not _hint_will_be_used(*grad_pre.shape, es, aligned, nz_rows):
             # the product below would gather every row: give the unwritten ones their zeros
             keep = unpack_row_flags(hint[0], grad_pre.shape[0])[:, None]
             grad_pre = torch.where(keep, grad_pre, torch.zeros_like(grad_pre[:1]))
