@@ -5,6 +5,8 @@ There is NO fallback: if the HIP library is missing or does not load, every prod
 import ctypes
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (GCN_SPMM_LIB: an experiment build of the same ABI — tools/build_gemm_variant.sh; never set in product use)
 LIB_PATH = os.environ.get("GCN_SPMM_LIB") or os.path.join(_HERE, "csrc", "libgcn_spmm.so")
@@ -59,22 +61,55 @@ class GcnGemmEpilogue(ctypes.Structure):
                 ("mask_bits", ctypes.c_void_p)]
 
 
-# every symbol include/gcn_spmm.h declares (tests check that the library exports all of them)
-EXPORTS = ("gcn_abi_version", "gcn_last_error", "gcn_plan_count_host", "gcn_plan_fill_host",
-           "gcn_spmm_workspace_bytes", "gcn_spmm_csr", "gcn_spmm_csr_ep",
-           "gcn_relu_dropout_backward", "gcn_csr_transpose_host",
-           "gcn_csr_transpose_workspace_bytes", "gcn_csr_transpose_device",
-           "gcn_row_normalize_device", "gcn_gemm_xw256_workspace_bytes", "gcn_gemm_xw256_f32",
-           "gcn_bwd_colsum_workspace_bytes", "gcn_relu_dropout_backward_colsum",
-           "gcn_log_softmax_backward_colsum", "gcn_plan_device_workspace_bytes",
-           "gcn_plan_count_device", "gcn_plan_fill_device", "gcn_coo_to_csr_workspace_bytes",
-           "gcn_coo_to_csr_device", "gcn_gemm_xw256_h2_workspace_bytes", "gcn_gemm_xw256_f32_h2",
-           "gcn_gemm_bf16_workspace_bytes", "gcn_gemm_xw_bf16",
-           "gcn_gemm_atg256_workspace_bytes", "gcn_gemm_atg256_f32",
-           "gcn_nll_log_softmax_backward_colsum", "gcn_gemm_atg_bf16_workspace_bytes",
-           "gcn_gemm_atg_bf16", "gcn_sddmm_csr", "gcn_rows_pack_count", "gcn_rows_pack_values",
-           "gcn_rows_unpack", "gcn_bits_row_counts", "gcn_gemm_xw256_b3_workspace_bytes",
-           "gcn_gemm_xw256_f32_b3", "gcn_gemm_atg256_f32_b3", "gcn_gemm_atg256_f32_b3_colsum")
+# every symbol include/gcn_spmm.h declares: name -> (restype, [argtypes]).  The ONE statement of the
+# C-ABI on the Python side: lib() binds exactly this, tests hold names and parameter counts against
+# the header (and check that the library exports all of them).
+i, i64, sz, f32, p = ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float, ctypes.c_void_p
+plan_p, ep_p = ctypes.POINTER(GcnCsrPlan), ctypes.POINTER(GcnEpilogue)
+gemm_ep_p = ctypes.POINTER(GcnGemmEpilogue)
+SIGNATURES = {
+    "gcn_abi_version": (i, []),
+    "gcn_last_error": (ctypes.c_char_p, []),
+    "gcn_plan_count_host": (i, [p, i, i64, i, i, c_i64p, c_i64p, c_i64p]),
+    "gcn_plan_fill_host": (i, [p, i, i64, i, i, p, i64, p, p, i64, p, p, i64]),
+    "gcn_plan_device_workspace_bytes": (sz, [i64]),
+    "gcn_plan_count_device": (i, [p, i, i64, i, i, p, sz, p, p]),
+    "gcn_plan_fill_device": (i, [p, i, i64, i, p, sz, p, i64, p, p, i64, p, p, i64, p]),
+    "gcn_spmm_workspace_bytes": (sz, [plan_p, i64]),
+    "gcn_spmm_csr": (i, [plan_p, i, p, i64, p, i64, i64, p, i, p, sz, p]),
+    "gcn_spmm_csr_ep": (i, [plan_p, i, p, i64, p, i64, i64, ep_p, p, sz, p]),
+    "gcn_relu_dropout_backward": (i, [i, p, p, p, i64, f32, p]),
+    "gcn_bwd_colsum_workspace_bytes": (sz, [i64, i64, i]),
+    "gcn_log_softmax_backward_colsum": (i, [i, p, p, p, p, i64, i64, p, p, i, p, sz, p]),
+    "gcn_relu_dropout_backward_colsum": (i, [i, p, p, p, p, i64, i64, f32, p, p, i, p, sz, p]),
+    "gcn_nll_log_softmax_backward_colsum": (i, [i, p, p, p, p, p, i64, i64, p, sz, p]),
+    "gcn_sddmm_csr": (i, [plan_p, i, p, i64, p, i64, i64, p, p]),
+    "gcn_csr_transpose_host": (i, [p, i, p, p, i64, i64, p, p, p]),
+    "gcn_csr_transpose_workspace_bytes": (sz, [i64, i64, i64]),
+    "gcn_csr_transpose_device": (i, [p, i, p, p, i64, i64, i64, p, p, p, p, sz, p]),
+    "gcn_coo_to_csr_workspace_bytes": (sz, [i64, i64, i64]),
+    "gcn_coo_to_csr_device": (i, [p, p, p, i64, i64, i64, i, p, i, p, p, p, p, sz, p]),
+    "gcn_row_normalize_device": (i, [p, i, p, i64, p]),
+    "gcn_gemm_xw256_workspace_bytes": (sz, []),
+    "gcn_gemm_xw256_f32": (i, [p, i64, p, i64, p, i64, i64, p, sz, p]),
+    "gcn_gemm_xw256_h2_workspace_bytes": (sz, []),
+    "gcn_gemm_xw256_f32_h2": (i, [p, i64, p, p, i64, p, i64, i64, p, p, gemm_ep_p, p, sz, p]),
+    "gcn_gemm_xw256_b3_workspace_bytes": (sz, []),
+    "gcn_gemm_xw256_f32_b3": (i, [p, i64, p, p, i64, p, i64, i64, p, gemm_ep_p, p, sz, p]),
+    "gcn_gemm_bf16_workspace_bytes": (sz, [i64, i64]),
+    "gcn_gemm_xw_bf16": (i, [p, i64, p, i64, p, i64, i64, i64, i64, gemm_ep_p, p, sz, p]),
+    "gcn_gemm_atg256_workspace_bytes": (sz, [i64]),
+    "gcn_gemm_atg256_f32": (i, [p, i64, p, p, i64, p, i64, p, p, p, i64, p, sz, p]),
+    "gcn_gemm_atg256_f32_b3": (i, [p, i64, p, p, i64, p, i64, p, i64, p, sz, p]),
+    "gcn_gemm_atg256_f32_b3_colsum": (i, [p, i64, p, p, i64, p, i64, p, i64, p, p, sz, p]),
+    "gcn_gemm_atg_bf16_workspace_bytes": (sz, [i64, i64, i64]),
+    "gcn_gemm_atg_bf16": (i, [p, i64, p, p, i64, p, i64, i64, i64, p, i64, p, sz, p]),
+    "gcn_rows_pack_count": (i, [i, p, i64, p, i64, i64, p, p, p]),
+    "gcn_rows_pack_values": (i, [i, p, i64, p, i64, i64, p, p, p]),
+    "gcn_rows_unpack": (i, [i, p, p, p, i64, i64, p, i64, p]),
+    "gcn_bits_row_counts": (i, [p, i64, i64, p, p]),
+}
+EXPORTS = tuple(SIGNATURES)
 
 _lib = None
 
@@ -95,150 +130,9 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:   # e.g. libamdhip64 not found
         raise NativeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    L.gcn_abi_version.restype = ctypes.c_int
-    L.gcn_last_error.restype = ctypes.c_char_p
-    L.gcn_plan_count_host.restype = ctypes.c_int
-    L.gcn_plan_count_host.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
-                                      ctypes.c_int32, ctypes.c_int32, c_i64p, c_i64p, c_i64p]
-    L.gcn_plan_fill_host.restype = ctypes.c_int
-    L.gcn_plan_fill_host.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
-                                     ctypes.c_int32, ctypes.c_int32,
-                                     ctypes.c_void_p, ctypes.c_int64,
-                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
-    L.gcn_spmm_workspace_bytes.restype = ctypes.c_size_t
-    L.gcn_spmm_workspace_bytes.argtypes = [ctypes.POINTER(GcnCsrPlan), ctypes.c_int64]
-    L.gcn_spmm_csr.restype = ctypes.c_int
-    L.gcn_spmm_csr.argtypes = [ctypes.POINTER(GcnCsrPlan), ctypes.c_int, ctypes.c_void_p,
-                               ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                               ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
-                               ctypes.c_void_p]
-    L.gcn_spmm_csr_ep.restype = ctypes.c_int
-    L.gcn_spmm_csr_ep.argtypes = [ctypes.POINTER(GcnCsrPlan), ctypes.c_int, ctypes.c_void_p,
-                                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                  ctypes.POINTER(GcnEpilogue), ctypes.c_void_p, ctypes.c_size_t,
-                                  ctypes.c_void_p]
-    L.gcn_relu_dropout_backward.restype = ctypes.c_int
-    L.gcn_relu_dropout_backward.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
-                                            ctypes.c_void_p]
-    L.gcn_csr_transpose_host.restype = ctypes.c_int
-    L.gcn_csr_transpose_host.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    L.gcn_csr_transpose_workspace_bytes.restype = ctypes.c_size_t
-    L.gcn_csr_transpose_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]
-    L.gcn_csr_transpose_device.restype = ctypes.c_int
-    L.gcn_csr_transpose_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                           ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                           ctypes.c_void_p]
-    L.gcn_row_normalize_device.restype = ctypes.c_int
-    L.gcn_row_normalize_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                           ctypes.c_int64, ctypes.c_void_p]
-    L.gcn_bwd_colsum_workspace_bytes.restype = ctypes.c_size_t
-    L.gcn_bwd_colsum_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]
-    L.gcn_relu_dropout_backward_colsum.restype = ctypes.c_int
-    L.gcn_relu_dropout_backward_colsum.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_void_p,
-                                                   ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                                   ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_int,
-                                                   ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    L.gcn_log_softmax_backward_colsum.restype = ctypes.c_int
-    L.gcn_log_softmax_backward_colsum.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_int,
-                                                  ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    L.gcn_nll_log_softmax_backward_colsum.restype = ctypes.c_int
-    L.gcn_nll_log_softmax_backward_colsum.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                      ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                                                      ctypes.c_size_t, ctypes.c_void_p]
-    L.gcn_gemm_xw256_workspace_bytes.restype = ctypes.c_size_t
-    L.gcn_gemm_xw256_workspace_bytes.argtypes = []
-    L.gcn_gemm_xw256_f32.restype = ctypes.c_int
-    L.gcn_gemm_xw256_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
-                                     ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                                     ctypes.c_size_t, ctypes.c_void_p]
-    L.gcn_plan_device_workspace_bytes.restype = ctypes.c_size_t
-    L.gcn_plan_device_workspace_bytes.argtypes = [ctypes.c_int64]
-    L.gcn_plan_count_device.restype = ctypes.c_int
-    L.gcn_plan_count_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int32,
-                                        ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t,
-                                        ctypes.c_void_p, ctypes.c_void_p]
-    L.gcn_plan_fill_device.restype = ctypes.c_int
-    L.gcn_plan_fill_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int32,
-                                       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
-                                       ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
-    L.gcn_coo_to_csr_workspace_bytes.restype = ctypes.c_size_t
-    L.gcn_coo_to_csr_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]
-    L.gcn_coo_to_csr_device.restype = ctypes.c_int
-    L.gcn_coo_to_csr_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
-                                        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                        ctypes.c_void_p]
-    L.gcn_gemm_xw256_h2_workspace_bytes.restype = ctypes.c_size_t
-    L.gcn_gemm_xw256_h2_workspace_bytes.argtypes = []
-    L.gcn_gemm_xw256_f32_h2.restype = ctypes.c_int
-    L.gcn_gemm_xw256_f32_h2.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(GcnGemmEpilogue),
-                                        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    L.gcn_gemm_xw256_b3_workspace_bytes.restype = ctypes.c_size_t
-    L.gcn_gemm_xw256_b3_workspace_bytes.argtypes = []
-    L.gcn_gemm_xw256_f32_b3.restype = ctypes.c_int
-    L.gcn_gemm_xw256_f32_b3.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                        ctypes.c_void_p, ctypes.POINTER(GcnGemmEpilogue),
-                                        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    L.gcn_gemm_atg256_f32_b3.restype = ctypes.c_int
-    L.gcn_gemm_atg256_f32_b3.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                         ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                         ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    L.gcn_gemm_atg256_f32_b3_colsum.restype = ctypes.c_int
-    L.gcn_gemm_atg256_f32_b3_colsum.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                                ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                                ctypes.c_void_p]
-    L.gcn_gemm_bf16_workspace_bytes.restype = ctypes.c_size_t
-    L.gcn_gemm_bf16_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
-    L.gcn_gemm_xw_bf16.restype = ctypes.c_int
-    L.gcn_gemm_xw_bf16.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
-                                   ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                   ctypes.c_int64, ctypes.POINTER(GcnGemmEpilogue), ctypes.c_void_p,
-                                   ctypes.c_size_t, ctypes.c_void_p]
-    L.gcn_gemm_atg256_workspace_bytes.restype = ctypes.c_size_t
-    L.gcn_gemm_atg256_workspace_bytes.argtypes = [ctypes.c_int64]
-    L.gcn_gemm_atg256_f32.restype = ctypes.c_int
-    L.gcn_gemm_atg256_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                      ctypes.c_size_t, ctypes.c_void_p]
-    L.gcn_gemm_atg_bf16_workspace_bytes.restype = ctypes.c_size_t
-    L.gcn_gemm_atg_bf16_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]
-    L.gcn_gemm_atg_bf16.restype = ctypes.c_int
-    L.gcn_gemm_atg_bf16.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                    ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                    ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                    ctypes.c_size_t, ctypes.c_void_p]
-    L.gcn_sddmm_csr.restype = ctypes.c_int
-    L.gcn_sddmm_csr.argtypes = [ctypes.POINTER(GcnCsrPlan), ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
-                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                                ctypes.c_void_p]
-    vp, i64 = ctypes.c_void_p, ctypes.c_int64
-    L.gcn_rows_pack_count.restype = ctypes.c_int
-    L.gcn_rows_pack_count.argtypes = [ctypes.c_int, vp, i64, vp, i64, i64, vp, vp, vp]
-    L.gcn_rows_pack_values.restype = ctypes.c_int
-    L.gcn_rows_pack_values.argtypes = [ctypes.c_int, vp, i64, vp, i64, i64, vp, vp, vp]
-    L.gcn_rows_unpack.restype = ctypes.c_int
-    L.gcn_rows_unpack.argtypes = [ctypes.c_int, vp, vp, vp, i64, i64, vp, i64, vp]
-    L.gcn_bits_row_counts.restype = ctypes.c_int
-    L.gcn_bits_row_counts.argtypes = [vp, i64, i64, vp, vp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.gcn_abi_version() != GCN_ABI_VERSION:
         raise NativeLibraryError(f"{LIB_PATH}: ABI version {L.gcn_abi_version()} != "
                                  f"{GCN_ABI_VERSION}; rebuild with `python -m pygcn_amd.build`")
@@ -251,3 +145,16 @@ def check(rc, what):
     if rc != 0:
         msg = lib().gcn_last_error()
         raise RuntimeError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
+
+
+def launch(name, device, *args, workspace=None):
+    """Call the launching entry point `name` with `args` on `device`'s current stream and raise if it
+    fails.  The header's rule this relies on: `void *stream` is the LAST parameter of every entry
+    point that launches, and those with a workspace end in `void *workspace, size_t workspace_bytes,
+    void *stream` — `workspace=n` (the answer of the entry point's *_workspace_bytes query) allocates
+    n bytes on `device` and passes them there, NULL when n is 0."""
+    with torch.cuda.device(device):
+        if workspace is not None:
+            ws = torch.empty(workspace, dtype=torch.uint8, device=device) if workspace else None
+            args += (ws.data_ptr() if workspace else None, workspace)
+        check(getattr(lib(), name)(*args, torch.cuda.current_stream().cuda_stream), name)

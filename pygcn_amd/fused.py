@@ -44,9 +44,9 @@ import weakref
 import torch
 
 from .graph import CSRGraph
-from . import spmm as _spmm
-from .spmm import (_dense_forward, _weight_grad, gemm_xw256, log_softmax_fusable, pack_row_flags,
-                   spmm_csr)
+from . import gemm as _gemm, spmm as _spmm
+from .gemm import _dense_forward, _weight_grad, gemm_xw256
+from .spmm import log_softmax_fusable, pack_row_flags, spmm_csr
 
 
 def _describe_rows(rs, rows):
@@ -64,7 +64,7 @@ def _list_rows2(rs, rows2):
     mask rows of the grad_input GEMM), rows2_padded (the weight-gradient kernel's list)."""
     rs.rows2, rs.n2 = rows2, int(rows2.numel())
     rs.rows2_i32 = rows2.to(torch.int32)
-    rs.rows2_padded = _spmm.padded_row_list(rows2)
+    rs.rows2_padded = _gemm.padded_row_list(rows2)
 
 
 class RowSets:
@@ -180,8 +180,8 @@ def _gcn2_forward(ctx, x, w1, b1, w2, b2, graph, dropout_p, seed):
     # bounds of max|operand| for the scaled fp16 GEMMs (set_gemm_scheme("h2") only; the default
     # three-part bf16 GEMMs need none), without a pass over the data:
     # X is constant (cached), and |Â·B| <= ‖Â‖∞·max|B|
-    bounded = x.dtype == torch.float32 and _spmm.gemm_needs_bounds()
-    ctx.x_bound = _spmm.absmax_cached(x) if bounded else None
+    bounded = x.dtype == torch.float32 and _gemm.gemm_needs_bounds()
+    ctx.x_bound = _gemm.absmax_cached(x) if bounded else None
     # Layer 1 REASSOCIATED when a GEMM kernel can carry the layer's epilogue (256 -> 256 fp32;
     # bf16 128 -> 128 / 256):
     #     h1 = dropout(relu((Â·X)·W1 + b1))        instead of   dropout(relu(Â·(X·W1) + b1))
@@ -189,7 +189,7 @@ def _gcn2_forward(ctx, x, w1, b1, w2, b2, graph, dropout_p, seed):
     # width, a GEMM), but the product z = Â·X of THIS forward pass is then all the backward
     # pass needs for grad_W1 = zᵀ·grad_pre1: no second sparse product for layer 1 (12.7 ms at
     # C4, 35.5 ms at C5).
-    ctx.reassoc = bool(_spmm.layer_gemm_reassociable(x, w1, b1))
+    ctx.reassoc = bool(_gemm.layer_gemm_reassociable(x, w1, b1))
     ctx.keep_bits = None
     h1 = h_bound = z = None
     ctx.z_bound = None
@@ -200,9 +200,9 @@ def _gcn2_forward(ctx, x, w1, b1, w2, b2, graph, dropout_p, seed):
             h_bound = torch.zeros(1, dtype=torch.float32, device=x.device)   # max|h1|, exact
         # `h1 > 0` — all the backward of ReLU / dropout asks of h1 — as one bit per element, written by the
         # same launch where it can: the masked grad_input GEMM then reads 32 bytes per row instead of 1 KiB
-        if _spmm.gemm_keep_bits_usable(z, None, dropout_p) and any(ctx.needs_input_grad):
+        if _gemm.gemm_keep_bits_usable(z, None, dropout_p) and any(ctx.needs_input_grad):
             ctx.keep_bits = torch.empty((z.shape[0], 8), dtype=torch.int32, device=z.device)
-        h1 = _spmm.layer_gemm(z, w1, ctx.z_bound, h_bound, bias=b1, relu=True, dropout_p=dropout_p,
+        h1 = _gemm.layer_gemm(z, w1, ctx.z_bound, h_bound, bias=b1, relu=True, dropout_p=dropout_p,
                               seed=seed, keep_bits_out=ctx.keep_bits)
         if h1 is None:                     # (alignment the kernel cannot take)
             ctx.reassoc, z, h_bound, ctx.keep_bits = False, None, None, None
@@ -296,12 +296,12 @@ def _hidden_layer_stage(h1, w2, grad_sup2, gs_bound, z, need_w2, need_w1, b1_dty
                 zeros(h1.shape[1], grad_sup2.shape[1]) if need_w2 else None,
                 zeros(h1.shape[1], dtype=b1_dtype) if b1_dtype is not None else None,
                 zeros(z.shape[1], h1.shape[1]) if (z is not None and need_w1) else None)
-    l2_fast = f32 and _spmm.gemm_handwritten() and grad_sup2.shape[1] == 256 and h1.shape[1] == 256
+    l2_fast = f32 and _gemm.gemm_handwritten() and grad_sup2.shape[1] == 256 and h1.shape[1] == 256
     l1_kernels = l2_fast or not f32 or not l1_follows_l2
     grad_w2 = grad_b1 = grad_w1 = h1c = None
     if need_w2:
         # (fp32 256 x 256, or bf16 128 x 128: rows of h1 read in place through the list)
-        grad_w2 = _spmm.weight_grad_rows(h1, grad_sup2, rows2_padded, None, h_bound, gs_bound, n_list=n2)
+        grad_w2 = _gemm.weight_grad_rows(h1, grad_sup2, rows2_padded, None, h_bound, gs_bound, n_list=n2)
         if grad_w2 is None:
             h1c = h1 if rows2 is None else h1.index_select(0, rows2)
             grad_w2 = _weight_grad(h1c, grad_sup2)
@@ -310,7 +310,7 @@ def _hidden_layer_stage(h1, w2, grad_sup2, gs_bound, z, need_w2, need_w1, b1_dty
     gpre1 = gemm_xw256(grad_sup2, w2t, gs_bound, gh_max, mask_src=h1, mask_rows=rows2_i32,
                        mask_bits=keep_bits, mask_scale=scale)
     if gpre1 is None:                                  # (C5: the bf16 GEMM carries the mask in its store too)
-        gpre1 = _spmm.gemm_bf16(grad_sup2, w2t, mask_src=h1, mask_rows=rows2_i32, mask_scale=scale)
+        gpre1 = _gemm.gemm_bf16(grad_sup2, w2t, mask_src=h1, mask_rows=rows2_i32, mask_scale=scale)
     if gpre1 is None:
         gh1 = _dense_forward(grad_sup2, w2t, gs_bound, gh_max)
         if rows2 is None:
@@ -325,7 +325,7 @@ def _hidden_layer_stage(h1, w2, grad_sup2, gs_bound, z, need_w2, need_w1, b1_dty
     del h1c
     if b1_dtype is not None and z is not None and need_w1 and l1_kernels:
         # grad_W1 and grad_b1 from ONE pass over grad_pre1: the weight-gradient kernel sums the rows it loads
-        both = _spmm.weight_grad_rows(z, gpre1, rows2_padded, None, z_bound, gh_max, n_list=n2, colsum_g=True)
+        both = _gemm.weight_grad_rows(z, gpre1, rows2_padded, None, z_bound, gh_max, n_list=n2, colsum_g=True)
         if both is not None:
             grad_w1, grad_b1 = both[0], both[1].to(b1_dtype)
     if b1_dtype is not None and grad_b1 is None:
@@ -333,7 +333,7 @@ def _hidden_layer_stage(h1, w2, grad_sup2, gs_bound, z, need_w2, need_w1, b1_dty
         grad_b1 = (sums[1] if sums is not None else gpre1.float().sum(0)).to(b1_dtype)
     if z is not None and need_w1 and grad_w1 is None:
         if l1_kernels:
-            grad_w1 = _spmm.weight_grad_rows(z, gpre1, rows2_padded, None, z_bound, gh_max, n_list=n2)
+            grad_w1 = _gemm.weight_grad_rows(z, gpre1, rows2_padded, None, z_bound, gh_max, n_list=n2)
         if grad_w1 is None:
             grad_w1 = _weight_grad(z if rows2 is None else z.index_select(0, rows2), gpre1)
     return gpre1, gh_max, grad_w2, grad_b1, grad_w1
@@ -380,9 +380,9 @@ def _gcn2_backward_rows(ctx, x, w1, w2, h1, out_rows, rs, grad_rows, needs):
             # grad_W1 = (Â·X)[R2]ᵀ · grad_pre1[R2]: a forward product restricted to rows R2
             z = spmm_csr(graph, x, tag="bwd_l1", c_select=rs.hint2[0],
                          out=_spmm._maybe_poisoned((n, x.shape[1]), x.dtype, dev))
-            if f32 and _spmm.gemm_handwritten() and x.shape[1] == 256 and gpre1.shape[1] == 256:
+            if f32 and _gemm.gemm_handwritten() and x.shape[1] == 256 and gpre1.shape[1] == 256:
                 z_bound = graph.inf_norm() * ctx.x_bound * 1.0001 if ctx.x_bound is not None else None
-                grad_w1 = _spmm.weight_grad_rows(z, gpre1, rs.rows2_padded, None, z_bound,
+                grad_w1 = _gemm.weight_grad_rows(z, gpre1, rs.rows2_padded, None, z_bound,
                                                  gpre_bound, n_list=rs.n2)
             if grad_w1 is None:
                 grad_w1 = _weight_grad(z.index_select(0, rs.rows2), gpre1)

@@ -133,17 +133,12 @@ class CSRGraph:
         col_out = torch.empty(nnz, dtype=torch.int32, device=device)
         val_out = torch.empty(nnz, dtype=torch.float32, device=device)
         nnz_out = torch.zeros(1, dtype=torch.int64, device=device)
-        ws_bytes = L.gcn_coo_to_csr_workspace_bytes(n_rows, n_cols, nnz)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            rc = L.gcn_coo_to_csr_device(
-                row.data_ptr(), col.data_ptr(), val.data_ptr(), nnz, n_rows, n_cols,
-                {"sum": _native.GCN_REDUCE_SUM, "max": _native.GCN_REDUCE_MAX}[reduce],
-                rowptr.data_ptr(), is64, col_out.data_ptr(), val_out.data_ptr(), nnz_out.data_ptr(),
-                ws.data_ptr(), ws_bytes, torch.cuda.current_stream().cuda_stream)
-        _native.check(rc, "gcn_coo_to_csr_device")
+        _native.launch("gcn_coo_to_csr_device", device,
+                       row.data_ptr(), col.data_ptr(), val.data_ptr(), nnz, n_rows, n_cols,
+                       {"sum": _native.GCN_REDUCE_SUM, "max": _native.GCN_REDUCE_MAX}[reduce],
+                       rowptr.data_ptr(), is64, col_out.data_ptr(), val_out.data_ptr(), nnz_out.data_ptr(),
+                       workspace=L.gcn_coo_to_csr_workspace_bytes(n_rows, n_cols, nnz))
         k = int(nnz_out.item())                     # one 8-byte read: the number of distinct entries
-        del ws
         if k < nnz:                                 # give the unused capacity back
             col_out, val_out = col_out[:k].clone(), val_out[:k].clone()
         return cls(rowptr, col_out, val_out, (n_rows, n_cols), validate=False, **kw)
@@ -257,24 +252,21 @@ class CSRGraph:
         ws_bytes = L.gcn_plan_device_workspace_bytes(n_rows)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         counts = torch.zeros(3, dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream().cuda_stream
-            _native.check(L.gcn_plan_count_device(self.rowptr.data_ptr(), is64, n_rows,
-                                                  self.item_cost, long_thresh, ws.data_ptr(),
-                                                  ws_bytes, counts.data_ptr(), stream),
-                          "gcn_plan_count_device")
-            ni, nc, nl = (int(v) for v in counts.tolist())
-            keep = {"items": torch.empty(max(2 * ni, 1), dtype=torch.int32, device=dev),
-                    "chunk_row": torch.empty(max(nc, 1), dtype=torch.int32, device=dev),
-                    "chunk_e0": torch.empty(max(nc, 1), dtype=torch.int64, device=dev),
-                    "long_row": torch.empty(max(nl, 1), dtype=torch.int32, device=dev),
-                    "long_chunk0": torch.empty(nl + 1, dtype=torch.int32, device=dev),
-                    "n_items": ni, "n_chunks": nc, "n_long": nl}
-            _native.check(L.gcn_plan_fill_device(
-                self.rowptr.data_ptr(), is64, n_rows, long_thresh, ws.data_ptr(), ws_bytes,
-                keep["items"].data_ptr(), ni, keep["chunk_row"].data_ptr(),
-                keep["chunk_e0"].data_ptr(), nc, keep["long_row"].data_ptr(),
-                keep["long_chunk0"].data_ptr(), nl, stream), "gcn_plan_fill_device")
+        # (the two planner calls take their workspace mid-list, and share it)
+        _native.launch("gcn_plan_count_device", dev, self.rowptr.data_ptr(), is64, n_rows, self.item_cost,
+                       long_thresh, ws.data_ptr(), ws_bytes, counts.data_ptr())
+        ni, nc, nl = (int(v) for v in counts.tolist())
+        keep = {"items": torch.empty(max(2 * ni, 1), dtype=torch.int32, device=dev),
+                "chunk_row": torch.empty(max(nc, 1), dtype=torch.int32, device=dev),
+                "chunk_e0": torch.empty(max(nc, 1), dtype=torch.int64, device=dev),
+                "long_row": torch.empty(max(nl, 1), dtype=torch.int32, device=dev),
+                "long_chunk0": torch.empty(nl + 1, dtype=torch.int32, device=dev),
+                "n_items": ni, "n_chunks": nc, "n_long": nl}
+        _native.launch("gcn_plan_fill_device", dev,
+                       self.rowptr.data_ptr(), is64, n_rows, long_thresh, ws.data_ptr(), ws_bytes,
+                       keep["items"].data_ptr(), ni, keep["chunk_row"].data_ptr(),
+                       keep["chunk_e0"].data_ptr(), nc, keep["long_row"].data_ptr(),
+                       keep["long_chunk0"].data_ptr(), nl)
         return keep
 
     def plan_arrays_host_planner(self):
@@ -302,16 +294,11 @@ class CSRGraph:
             rowptr_t = torch.empty(n_cols + 1, dtype=self.rowptr.dtype, device=dev)
             col_t = torch.empty(self.nnz, dtype=torch.int32, device=dev)
             val_t = torch.empty(self.nnz, dtype=torch.float32, device=dev)
-            ws_bytes = L.gcn_csr_transpose_workspace_bytes(n_rows, n_cols, self.nnz)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                rc = L.gcn_csr_transpose_device(
-                    self.rowptr.data_ptr(), int(self.rowptr.dtype == torch.int64),
-                    self.col.data_ptr(), self.val.data_ptr(), n_rows, n_cols, self.nnz,
-                    rowptr_t.data_ptr(), col_t.data_ptr(), val_t.data_ptr(), ws.data_ptr(),
-                    ws_bytes, torch.cuda.current_stream().cuda_stream)
-            _native.check(rc, "gcn_csr_transpose_device")
-            del ws
+            _native.launch("gcn_csr_transpose_device", dev,
+                           self.rowptr.data_ptr(), int(self.rowptr.dtype == torch.int64),
+                           self.col.data_ptr(), self.val.data_ptr(), n_rows, n_cols, self.nnz,
+                           rowptr_t.data_ptr(), col_t.data_ptr(), val_t.data_ptr(),
+                           workspace=L.gcn_csr_transpose_workspace_bytes(n_rows, n_cols, self.nnz))
             g = CSRGraph(rowptr_t, col_t, val_t, (n_cols, n_rows), item_cost=self.item_cost,
                          long_thresh=self.long_thresh, validate=False)
             g._t, g._t_val_version = self, val_t._version
@@ -323,11 +310,8 @@ class CSRGraph:
         `normalize(mx)` (pygcn/utils.py:390-397); rows whose sum has an infinite float32
         reciprocal (0, or a subnormal below 2^-128) become 0, as there.  Invalidates the cached
         transpose."""
-        with torch.cuda.device(self.device):
-            rc = _native.lib().gcn_row_normalize_device(
-                self.rowptr.data_ptr(), int(self.rowptr.dtype == torch.int64),
-                self.val.data_ptr(), self.shape[0], torch.cuda.current_stream().cuda_stream)
-        _native.check(rc, "gcn_row_normalize_device")
+        _native.launch("gcn_row_normalize_device", self.device, self.rowptr.data_ptr(),
+                       int(self.rowptr.dtype == torch.int64), self.val.data_ptr(), self.shape[0])
         self._t = None
         return self
 

@@ -20,8 +20,9 @@ from torch.nn.parameter import Parameter
 if not __package__:   # imported flat, the reference's convention (`from layers import ...`)
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pygcn_amd.graph import CSRGraph, _require_cuda, as_graph  # noqa: E402
-from pygcn_amd.spmm import (DenseMMFunction, GraphConvFunction, SpMMFunction,  # noqa: E402
-                            dropout_seed_for, log_softmax_fusable)
+from pygcn_amd.gemm import DenseMMFunction  # noqa: E402
+from pygcn_amd.spmm import (GraphConvFunction, SpMMFunction, dropout_seed_for,  # noqa: E402
+                            log_softmax_fusable)
 from pygcn_amd.sharded import (ShardedGraph, ShardedHiddenLayerFunction,  # noqa: E402
                                ShardedInputLayerFunction, ShardedSpMMFunction)
 

@@ -148,7 +148,7 @@ def forward_exchange_ab(sg, h_local, weight, bias, modes, reps=3, log_softmax=Tr
     after one warm-up, each bracketed by a barrier; the figure of a mode is the slowest rank's
     mean.  Leaves the graph in the FASTEST mode (the same on every rank: the times are
     all-reduced) and returns {"ms": {mode: ms}, "chosen": mode}.  Collective."""
-    from .spmm import _dense_forward
+    from .gemm import _dense_forward
     dev = h_local.device
     cuda = dev.type == "cuda"
     kw = {"log_softmax": True} if log_softmax else {}

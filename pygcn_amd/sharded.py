@@ -57,9 +57,11 @@ import torch
 import torch.distributed as dist
 
 from . import tuning
+from .gemm import (_dense_forward, _dense_grads, _weight_grad, absmax_cached, known_absmax, layer_gemm,
+                   layer_gemm_reassociable, remember_absmax)
 from .graph import CSRGraph
-from .spmm import (_dense_forward, _grad_pre_and_bias, _weight_grad, check_fused_epilogue, dropout_scale,
-                   pack_row_flags, rows_pack, rows_unpack, spmm_csr, unpack_row_flags)
+from .spmm import (_grad_pre_and_bias, check_fused_epilogue, dropout_scale, dropout_seed_for, pack_row_flags,
+                   rows_pack, rows_unpack, spmm_csr, unpack_row_flags)
 
 
 def partition_rows(rowptr, world):
@@ -763,7 +765,6 @@ class ShardedGraph:
         Pipelined like product(): the own-rows GEMM and the product over the entries that
         reference own rows run while the compressed rows are in flight.  Same result as
         product(h·W) up to fp32 summation order."""
-        from .spmm import _dense_forward as gemm
         ev = self._tic(h_local)
         h = self.halo
         kw = {"dropout_p": dropout_p, "seed": seed, "row_base": self.r0} if dropout_p > 0.0 else {}
@@ -774,7 +775,7 @@ class ShardedGraph:
         h_halo = None
         if not self.overlap:                  # (--no-overlap is an A/B switch here too)
             h_halo = h.exchange_compressed_end(state, h_local)
-        sup_own = gemm(h_local, weight, h_bound)
+        sup_own = _dense_forward(h_local, weight, h_bound)
         part = self._spmm(a_own, sup_own, tag="fwd_local")            # overlaps the transfers
         ev_w = self._tic(h_local)
         if h_halo is None:
@@ -784,7 +785,7 @@ class ShardedGraph:
         #  cover them, and the scaled fp16 scheme overflows silently above 2-4x its bound.  No bound:
         #  gemm_xw256 takes one absmax pass over the small halo block under "h2"; the default
         #  three-part bf16 scheme needs none.)
-        sup_halo = gemm(h_halo, weight, None) if h_halo.shape[0] else \
+        sup_halo = _dense_forward(h_halo, weight, None) if h_halo.shape[0] else \
             h_halo.new_empty((0, weight.shape[1]))
         out = self._spmm(a_halo, sup_halo, bias=bias, relu=relu, tag="fwd_local", B2=part, **kw)
         self.last_recv_bytes["fwd"] = h.last_recv_bytes
@@ -888,7 +889,6 @@ class ShardedHiddenLayerFunction(torch.autograd.Function):
         ctx.relu, ctx.log_softmax = bool(relu), bool(log_softmax)
         ctx.last_layer = bool(last_layer or log_softmax)
         ctx.scale = dropout_scale(dropout_p)
-        from .spmm import known_absmax
         bound = known_absmax(h_local) if (h_local.is_cuda and h_local.dtype == torch.float32) else None
         out = sg.product_hidden(h_local, weight, bias=bias, relu=relu, dropout_p=dropout_p, seed=seed,
                                 log_softmax=log_softmax, h_bound=bound)
@@ -897,7 +897,6 @@ class ShardedHiddenLayerFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from .spmm import _dense_grads
         sg = ctx.sg
         h_local, weight = ctx.saved_tensors[:2]
         out = ctx.saved_tensors[2] if (ctx.relu or ctx.log_softmax) else None
@@ -939,7 +938,6 @@ class ShardedInputLayerFunction(torch.autograd.Function):
         # GEMM of the halo rows disappears), and z_r = Â_r·[X_r ; X_halo] of this forward pass is all
         # the backward pass needs for grad_W (no local product in backward either).
         out = z = None
-        from .spmm import absmax_cached, layer_gemm, layer_gemm_reassociable
         if sg._hinted_product and x_local.is_cuda and layer_gemm_reassociable(x_local, weight, bias):
             z = sg._spmm(sg.A, x_local, tag="fwd_local", B2=x_halo)
             sg._toc(ev, "fwd")       # (the window of the product, as in the other branch)
@@ -956,7 +954,6 @@ class ShardedInputLayerFunction(torch.autograd.Function):
             if out is None:
                 z = None
             elif y_max is not None:
-                from .spmm import remember_absmax
                 remember_absmax(out, y_max)          # the next layer's GEMM scales by it
         ctx.reassoc = out is not None
         if out is None:
@@ -980,7 +977,6 @@ class ShardedInputLayerFunction(torch.autograd.Function):
         if ctx.needs_input_grad[3] and ctx.reassoc:
             # (x_local is z_r = Â_r·X here.)  With both maxima known — ‖Â‖∞·max|X| and the maximum the
             # GEMM above this layer reported for grad_out — the gather-fused MFMA kernel runs
-            from .spmm import known_absmax
             g_bound = known_absmax(grad_out) if ctx.z_bound is not None else None
             grad_w = _weight_grad(x_local, grad_pre.contiguous(), ctx.z_bound,
                                   g_bound * ctx.scale if g_bound is not None else None)
@@ -1024,7 +1020,6 @@ class ShardedGCN(torch.nn.Module):
         if rows is None:
             return self.model(x_local, sg)
         from . import sharded_fused as sf
-        from .spmm import dropout_seed_for
         if not sf.fusable(sg, self.model, x_local):
             return self.model(x_local, sg)[rows.rows_user if isinstance(rows, sf.ShardedRowSets) else rows]
         if isinstance(rows, sf.ShardedRowSets):

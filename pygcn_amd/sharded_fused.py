@@ -24,10 +24,11 @@ the pipelined dense halo exchange and the log_softmax in the completing launch).
 import torch
 import torch.distributed as dist
 
-from . import spmm as _spmm
+from . import gemm as _gemm, spmm as _spmm
 from .fused import _hidden_layer_stage, _loss_rows_stage, _describe_rows, _list_rows2
 from .sharded import HaloExchange
-from .spmm import _dense_forward, log_softmax_fusable
+from .gemm import _dense_forward
+from .spmm import log_softmax_fusable
 
 
 class ShardedRowSets:
@@ -96,7 +97,7 @@ def fusable(sg, model, x_local):
     return (gc1 is not None and gc2 is not None and not hasattr(model, "gc3")
             and sg.exchange_mode == "halo" and sg._hinted_product and x_local.is_cuda
             and x_local.dim() == 2 and not x_local.requires_grad
-            and _spmm.layer_gemm_reassociable(x_local, gc1.weight, gc1.bias)
+            and _gemm.layer_gemm_reassociable(x_local, gc1.weight, gc1.bias)
             and log_softmax_fusable(gc2.out_features, gc2.weight.dtype))
 
 
@@ -119,10 +120,10 @@ class ShardedGCN2RowsFunction(torch.autograd.Function):
         kw = {"dropout_p": dropout_p, "seed": seed, "row_base": sg.r0} if dropout_p > 0.0 else {}
         # (`h1 > 0` as one bit per element for the masked grad_input GEMM: pygcn_amd/fused.py)
         ctx.keep_bits = None
-        if f32 and _spmm.gemm_keep_bits_usable(z, None, dropout_p) and any(ctx.needs_input_grad):
+        if f32 and _gemm.gemm_keep_bits_usable(z, None, dropout_p) and any(ctx.needs_input_grad):
             ctx.keep_bits = torch.empty((z.shape[0], 8), dtype=torch.int32, device=z.device)
             kw = dict(kw, keep_bits_out=ctx.keep_bits)
-        h1 = _spmm.layer_gemm(z, w1, ctx.z_bound, h_bound, bias=b1, relu=True, **kw)
+        h1 = _gemm.layer_gemm(z, w1, ctx.z_bound, h_bound, bias=b1, relu=True, **kw)
         if h1 is None:
             raise RuntimeError("sharded one-node path: the layer GEMM declined the operands")
         ctx.h_bound = h_bound

@@ -11,8 +11,14 @@ fallback exists: non-HIP tensors or a missing library raise.
 import torch
 
 from . import _native, tuning
+from .gemm import (_dense_forward, _dense_grads, _seed_fields, _weight_grad, absmax_cached, gemm_bf16,
+                   gemm_handwritten, gemm_needs_bounds, gemm_xw256, known_absmax, layer_gemm,
+                   layer_gemm_reassociable, padded_row_list, remember_absmax, weight_grad_rows)
+# (names of gemm.py that callers reach as pygcn_amd.spmm.<name>: bench.py and tests/conftest.py the scheme
+#  switch, code written against the module before the dense side moved out the other three)
+from .gemm import DenseMMFunction, gemm_keep_bits_usable, gemm_scheme, set_bound_check, set_gemm_scheme  # noqa: F401
 from .graph import CSRGraph, _require_cuda, as_graph
-from .tuning import K_SPLIT, MIN_ROWS, REASSOC_MAX_WIDTH_RATIO      # (dispatch thresholds: one table)
+from .tuning import MIN_ROWS, REASSOC_MAX_WIDTH_RATIO      # (dispatch thresholds: one table)
 
 _DTYPES = {torch.float32: _native.GCN_DTYPE_F32, torch.bfloat16: _native.GCN_DTYPE_BF16}
 
@@ -106,19 +112,14 @@ def spmm_csr(graph, B, bias=None, relu=False, out=None, tag="fwd", dropout_p=0.0
     plan = graph.plan(B.dtype)
     ws_bytes = L.gcn_spmm_workspace_bytes(plan, F)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=B.device) if ws_bytes else None
-    with torch.cuda.device(B.device):
-        stream = torch.cuda.current_stream().cuda_stream
+    with torch.cuda.device(B.device):      # (the timing events belong on the operand's device)
         rec = _timing_records
         if rec is not None:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-        seed_dev = None
-        if isinstance(seed, torch.Tensor):
-            if seed.dtype != torch.int64 or seed.numel() != 1 or seed.device != B.device:
-                raise RuntimeError("spmm_csr: a tensor seed must be one int64 on the operand's device")
-            seed_dev, seed = seed.data_ptr(), 0
+        seed, seed_dev = _seed_fields(seed, B.device, "spmm_csr")
         ep = _native.GcnEpilogue(bias.data_ptr() if bias is not None else None, int(bool(relu)),
-                                 float(dropout_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                 float(dropout_p), seed,
                                  b_hint[0].data_ptr() if b_hint is not None else None,
                                  b_hint[1].data_ptr() if b_hint is not None else None,
                                  B2.data_ptr() if B2 is not None and B2.numel() else None,
@@ -129,13 +130,11 @@ def spmm_csr(graph, B, bias=None, relu=False, out=None, tag="fwd", dropout_p=0.0
                                  c_select.data_ptr() if c_select is not None else None,
                                  int(bool(skip_zero_rows) and c_flags is not None), int(row_base),
                                  c_absmax.data_ptr() if c_absmax is not None else None)
-        rc = L.gcn_spmm_csr_ep(plan, _DTYPES[B.dtype], B.data_ptr(), B.stride(0) if F else 0,
-                               out.data_ptr(), out.stride(0), F, ep,
-                               ws.data_ptr() if ws is not None else None, ws_bytes, stream)
+        _native.launch("gcn_spmm_csr_ep", B.device, plan, _DTYPES[B.dtype], B.data_ptr(), B.stride(0) if F else 0,
+                       out.data_ptr(), out.stride(0), F, ep, ws.data_ptr() if ws is not None else None, ws_bytes)
         if rec is not None:
             ev1.record()
             rec.append((tag, ev0, ev1, graph))
-    _native.check(rc, "gcn_spmm_csr_ep")
     return out
 
 
@@ -159,11 +158,8 @@ def sddmm_csr(graph, G, B):
     out = torch.empty(graph.nnz, dtype=torch.float32, device=G.device)
     if graph.nnz == 0:
         return out
-    with torch.cuda.device(G.device):
-        rc = _native.lib().gcn_sddmm_csr(graph.plan(), _DTYPES[G.dtype], G.data_ptr(), G.stride(0),
-                                         B.data_ptr(), B.stride(0), G.shape[1], out.data_ptr(),
-                                         torch.cuda.current_stream().cuda_stream)
-    _native.check(rc, "gcn_sddmm_csr")
+    _native.launch("gcn_sddmm_csr", G.device, graph.plan(), _DTYPES[G.dtype], G.data_ptr(), G.stride(0),
+                   B.data_ptr(), B.stride(0), G.shape[1], out.data_ptr())
     return out
 
 
@@ -187,16 +183,11 @@ def rows_pack(src, rows=None):
     bits = torch.empty((m, F // 32), dtype=torch.int32, device=dev)
     counts = torch.empty(m, dtype=torch.int32, device=dev)
     offsets = torch.zeros(m + 1, dtype=torch.int64, device=dev)
-    L, dt = _native.lib(), _DTYPES[src.dtype]
-    rp = rows.data_ptr() if rows is not None else None
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream().cuda_stream
-        _native.check(L.gcn_rows_pack_count(dt, src.data_ptr(), src.stride(0), rp, m, F, bits.data_ptr(),
-                                            counts.data_ptr(), st), "gcn_rows_pack_count")
-        torch.cumsum(counts, 0, out=offsets[1:])
-        vals = torch.empty(int(offsets[-1]), dtype=src.dtype, device=dev)
-        _native.check(L.gcn_rows_pack_values(dt, src.data_ptr(), src.stride(0), rp, m, F, offsets.data_ptr(),
-                                             vals.data_ptr(), st), "gcn_rows_pack_values")
+    source = (_DTYPES[src.dtype], src.data_ptr(), src.stride(0), rows.data_ptr() if rows is not None else None, m, F)
+    _native.launch("gcn_rows_pack_count", dev, *source, bits.data_ptr(), counts.data_ptr())
+    torch.cumsum(counts, 0, out=offsets[1:])
+    vals = torch.empty(int(offsets[-1]), dtype=src.dtype, device=dev)
+    _native.launch("gcn_rows_pack_values", dev, *source, offsets.data_ptr(), vals.data_ptr())
     return bits, offsets, vals
 
 
@@ -214,13 +205,10 @@ def rows_unpack(bits, vals, F):
     counts = torch.empty(m, dtype=torch.int32, device=dev)
     offsets = torch.zeros(m + 1, dtype=torch.int64, device=dev)
     out = torch.empty((m, F), dtype=vals.dtype, device=dev)
-    L = _native.lib()
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream().cuda_stream
-        _native.check(L.gcn_bits_row_counts(bits.data_ptr(), m, F // 32, counts.data_ptr(), st), "gcn_bits_row_counts")
-        torch.cumsum(counts, 0, out=offsets[1:])
-        _native.check(L.gcn_rows_unpack(_DTYPES[vals.dtype], bits.data_ptr(), offsets.data_ptr(), vals.data_ptr(),
-                                        m, F, out.data_ptr(), out.stride(0), st), "gcn_rows_unpack")
+    _native.launch("gcn_bits_row_counts", dev, bits.data_ptr(), m, F // 32, counts.data_ptr())
+    torch.cumsum(counts, 0, out=offsets[1:])
+    _native.launch("gcn_rows_unpack", dev, _DTYPES[vals.dtype], bits.data_ptr(), offsets.data_ptr(), vals.data_ptr(),
+                   m, F, out.data_ptr(), out.stride(0))
     return out
 
 
@@ -242,11 +230,8 @@ def relu_dropout_backward(grad_out, out, scale=1.0):
         raise RuntimeError("relu_dropout_backward: dtype/shape mismatch")
     grad_out, out = grad_out.contiguous(), out.contiguous()
     res = torch.empty_like(grad_out)
-    with torch.cuda.device(grad_out.device):
-        rc = _native.lib().gcn_relu_dropout_backward(
-            _DTYPES[grad_out.dtype], grad_out.data_ptr(), out.data_ptr(), res.data_ptr(),
-            grad_out.numel(), float(scale), torch.cuda.current_stream().cuda_stream)
-    _native.check(rc, "gcn_relu_dropout_backward")
+    _native.launch("gcn_relu_dropout_backward", grad_out.device, _DTYPES[grad_out.dtype], grad_out.data_ptr(),
+                   out.data_ptr(), res.data_ptr(), grad_out.numel(), float(scale))
     return res
 
 
@@ -283,21 +268,16 @@ def backward_with_colsum(grad_out, out=None, scale=1.0, log_softmax=False, skip_
                 torch.empty(1, dtype=torch.int32, device=grad_out.device))
     skip = int(bool(skip_zero_rows) and hint is not None and out is not None)
     ws_bytes = L.gcn_bwd_colsum_workspace_bytes(n, F, _DTYPES[grad_out.dtype])
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=grad_out.device)
-    with torch.cuda.device(grad_out.device):
-        if log_softmax:
-            rc = L.gcn_log_softmax_backward_colsum(
-                _DTYPES[grad_out.dtype], grad_out.data_ptr(), out.data_ptr(), grad_pre.data_ptr(),
-                colsum.data_ptr(), n, F, hint[0].data_ptr(), hint[1].data_ptr(), skip,
-                ws.data_ptr(), ws_bytes, torch.cuda.current_stream().cuda_stream)
-        else:
-            rc = L.gcn_relu_dropout_backward_colsum(
-                _DTYPES[grad_out.dtype], grad_out.data_ptr(), out.data_ptr() if out is not None else None,
-                grad_pre.data_ptr() if out is not None else None, colsum.data_ptr(), n, F, float(scale),
-                hint[0].data_ptr() if hint else None, hint[1].data_ptr() if hint else None, skip,
-                ws.data_ptr(), ws_bytes, torch.cuda.current_stream().cuda_stream)
-    _native.check(rc, "gcn_log_softmax_backward_colsum" if log_softmax
-                  else "gcn_relu_dropout_backward_colsum")
+    if log_softmax:
+        _native.launch("gcn_log_softmax_backward_colsum", grad_out.device,
+                       _DTYPES[grad_out.dtype], grad_out.data_ptr(), out.data_ptr(), grad_pre.data_ptr(),
+                       colsum.data_ptr(), n, F, hint[0].data_ptr(), hint[1].data_ptr(), skip, workspace=ws_bytes)
+    else:
+        _native.launch("gcn_relu_dropout_backward_colsum", grad_out.device,
+                       _DTYPES[grad_out.dtype], grad_out.data_ptr(), out.data_ptr() if out is not None else None,
+                       grad_pre.data_ptr() if out is not None else None, colsum.data_ptr(), n, F, float(scale),
+                       hint[0].data_ptr() if hint else None, hint[1].data_ptr() if hint else None, skip,
+                       workspace=ws_bytes)
     return grad_pre, colsum.to(grad_out.dtype), hint
 
 
@@ -320,14 +300,10 @@ def nll_log_softmax_backward(logp, target, coef):
     n, F = logp.shape
     grad_pre = torch.empty_like(logp)
     colsum = torch.empty(F, dtype=torch.float32, device=logp.device)
-    ws_bytes = L.gcn_bwd_colsum_workspace_bytes(n, F, _DTYPES[logp.dtype])
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=logp.device)
-    with torch.cuda.device(logp.device):
-        rc = L.gcn_nll_log_softmax_backward_colsum(
-            _DTYPES[logp.dtype], target.data_ptr(), coef.data_ptr(), logp.data_ptr(),
-            grad_pre.data_ptr(), colsum.data_ptr(), n, F, ws.data_ptr(), ws_bytes,
-            torch.cuda.current_stream().cuda_stream)
-    _native.check(rc, "gcn_nll_log_softmax_backward_colsum")
+    _native.launch("gcn_nll_log_softmax_backward_colsum", logp.device,
+                   _DTYPES[logp.dtype], target.data_ptr(), coef.data_ptr(), logp.data_ptr(),
+                   grad_pre.data_ptr(), colsum.data_ptr(), n, F,
+                   workspace=L.gcn_bwd_colsum_workspace_bytes(n, F, _DTYPES[logp.dtype]))
     return grad_pre, colsum.to(logp.dtype)
 
 
@@ -482,515 +458,6 @@ class SpMMFunction(torch.autograd.Function):
         return None, grad_B, grad_bias, None, None, None
 
 
-def gemm_keep_bits_usable(X, rows=None, dropout_p=0.0):
-    """Does gemm_xw256 run this operand on the kernel that can write / read the ONE-BIT form of a ReLU /
-    dropout result (C-ABI gcn_gemm_epilogue.keep_bits_out / mask_bits: contiguous rows, the three-part
-    scheme, dropout_p in {0, 1/2})?"""
-    return (_gemm_scheme == "bf16x3" and rows is None and X.dtype == torch.float32 and X.is_cuda and X.dim() == 2
-            and X.shape[1] == 256 and X.stride(1) == 1 and X.stride(0) < (1 << 21) and dropout_p in (0.0, 0.5))
-
-
-def gemm_xw256(X, W, x_bound=None, y_absmax=None, rows=None, mask_src=None, mask_scale=1.0,
-               bias=None, relu=False, dropout_p=0.0, seed=0, mask_rows=None, row_base=0,
-               keep_bits_out=None, mask_bits=None):
-    """X[M,256] · W[256,256] through the hand-written MFMA kernels (fp32 in/out, fp32-level
-    accuracy).  None if the operands do not fit the kernels' fixed shape / alignment (the caller
-    then uses torch.mm — hipBLASLt).
-
-    Default scheme "bf16x3": C-ABI gcn_gemm_xw256_f32_b3 — three bf16 parts per operand, six MFMAs
-    per product: a 24-bit significand, the fp32-equivalent of the reference's `torch.mm`; no scaling,
-    `x_bound` is ignored.  Scheme "h2" (set_gemm_scheme; 22-bit significand, half the matrix work):
-    C-ABI gcn_gemm_xw256_f32_h2 — power-of-two scaling + two fp16 parts,
-    three MFMAs per product.  `x_bound` (DEVICE float tensor [1]) is any upper bound of max|X|; if
-    the caller has none, max|X| is computed here by one reduction pass.  `y_absmax` (DEVICE float
-    tensor [1], zeroed by the caller) receives max|Y|, from which a layer derives the next bound
-    without a pass over the data.  `rows` (int32 device list): output row r is the product of
-    input row rows[r] — a gather fused into the kernel's loads.  `mask_src` ([*, 256] fp32, read
-    at the same input rows, or — `mask_rows`, an int32 device list — at mask_rows[r] for output
-    row r): the store becomes mask_src > 0 ? y * mask_scale : 0, the backward of a
-    fused ReLU / dropout epilogue, in the GEMM's own store (None if it cannot be fused).
-    `bias` / `relu` / `dropout_p` / `seed`: FORWARD epilogue in the store, y = dropout(relu(acc +
-    bias)) with the same Philox keep function as the SpMM epilogue — for a layer evaluated as
-    (Â·X)·W + b, whose last stage is the GEMM (None if it cannot be fused).
-    `keep_bits_out` (int32 [M, 8], with relu; only where gemm_keep_bits_usable()): the launch also writes
-    `out > 0` as one bit per element; `mask_bits` (such a tensor, given NEXT TO mask_src): the backward mask
-    is read from the bits (32 bytes per row instead of 1 KiB) where the launch can, from mask_src where not.
-    Both schemes carry every option; "bf16x3" keeps full accuracy for 1e-30 <= |x| <= 3e38 (below
-    that its low-order parts underflow — tests/test_gemm_gpu.py)."""
-    if (_gemm_scheme == "exact" or X.dtype != torch.float32 or W.dtype != torch.float32 or not X.is_cuda
-            or X.dim() != 2 or tuple(W.shape) != (256, 256) or X.shape[1] != 256 or X.shape[0] == 0
-            or X.stride(1) != 1 or X.stride(0) % 4 or X.data_ptr() % 16 or W.stride(1) != 1):
-        return None
-    L = _native.lib()
-    has_fwd_ep = bias is not None or relu or dropout_p > 0.0
-    if has_fwd_ep and (mask_src is not None
-                       or (bias is not None and (bias.dtype != torch.float32 or bias.numel() != 256
-                                                 or not bias.is_contiguous() or bias.data_ptr() % 16))):
-        return None
-    if mask_src is not None and (mask_src.dtype != torch.float32
-                                 or mask_src.dim() != 2 or mask_src.shape[1] != 256
-                                 or mask_src.stride(1) != 1 or mask_src.stride(0) % 4
-                                 or mask_src.data_ptr() % 16 or mask_src.device != X.device):
-        return None
-    if mask_rows is not None and (mask_rows.dtype != torch.int32 or not mask_rows.is_contiguous()
-                                  or mask_rows.device != X.device
-                                  or mask_rows.numel() < (rows.numel() if rows is not None else X.shape[0])):
-        raise RuntimeError("gemm_xw256: mask_rows must be a contiguous int32 device list, one entry per output row")
-    if rows is not None:
-        if rows.dtype != torch.int32 or not rows.is_contiguous() or rows.device != X.device:
-            raise RuntimeError("gemm_xw256: rows must be a contiguous int32 device tensor")
-    m_out = rows.numel() if rows is not None else X.shape[0]
-    Y = torch.empty((m_out, 256), dtype=torch.float32, device=X.device)
-    if m_out == 0:
-        return Y
-    for t, name in ((keep_bits_out, "keep_bits_out"), (mask_bits, "mask_bits")):
-        if t is not None and (t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 8 or not t.is_contiguous()
-                              or t.device != X.device):
-            raise RuntimeError(f"gemm_xw256: {name} must be a contiguous int32 [rows, 8] device tensor")
-    if keep_bits_out is not None and not (relu and keep_bits_out.shape[0] >= m_out
-                                          and gemm_keep_bits_usable(X, rows, dropout_p)
-                                          and Y.stride(0) < (1 << 21)):
-        raise RuntimeError("gemm_xw256: keep_bits_out needs relu, contiguous rows, the bf16x3 scheme and "
-                           "dropout_p in {0, 1/2} (gemm_keep_bits_usable)")
-    if mask_bits is not None and (mask_src is None or not gemm_keep_bits_usable(X, rows)):
-        mask_bits = None                      # (this launch reads the mask itself)
-    if x_bound is None and _gemm_scheme == "h2":
-        # no bound known: one reduction pass over X (1.4 ms at M = 10^7) and the 5.4 ms kernel
-        # still beat the 7.5 ms three-part kernel — and keep full accuracy for tiny operands,
-        # where the third bf16 part would fall into the denormals
-        x_bound = torch.linalg.vector_norm(X.detach(), ord=float("inf")).reshape(1)
-    with torch.cuda.device(X.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        ep = None
-        if has_fwd_ep or mask_src is not None:
-            seed_dev = None
-            by_bits = mask_bits is not None
-            if isinstance(seed, torch.Tensor):       # device-resident seed (hipGraph capture)
-                seed_dev, seed = seed.data_ptr(), 0
-            ep = _native.GcnGemmEpilogue(
-                bias.detach().data_ptr() if bias is not None else None, int(bool(relu)),
-                float(dropout_p), int(seed) & 0xFFFFFFFFFFFFFFFF, seed_dev,
-                mask_src.data_ptr() if (mask_src is not None and not by_bits) else None,
-                mask_src.stride(0) if (mask_src is not None and not by_bits) else 0, float(mask_scale),
-                mask_rows.data_ptr() if (mask_rows is not None and mask_src is not None) else None,
-                int(row_base),
-                keep_bits_out.data_ptr() if keep_bits_out is not None else None,
-                mask_bits.data_ptr() if by_bits else None)
-        if _gemm_scheme == "h2":
-            if x_bound.dtype != torch.float32 or x_bound.numel() != 1 or x_bound.device != X.device:
-                raise RuntimeError("gemm_xw256: x_bound must be one float32 on the operand's device")
-            ws_bytes = L.gcn_gemm_xw256_h2_workspace_bytes()
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=X.device)
-            rc = L.gcn_gemm_xw256_f32_h2(X.data_ptr(), X.stride(0),
-                                         rows.data_ptr() if rows is not None else None,
-                                         W.data_ptr(), W.stride(0),
-                                         Y.data_ptr(), Y.stride(0), m_out, x_bound.data_ptr(),
-                                         y_absmax.data_ptr() if y_absmax is not None else None,
-                                         ep, ws.data_ptr(), ws_bytes, stream)
-            _native.check(rc, "gcn_gemm_xw256_f32_h2")
-            if _bound_check and y_absmax is not None and not bool(torch.isfinite(y_absmax).all()):
-                raise RuntimeError("gemm_xw256: non-finite output — x_bound was smaller than max|X| (the "
-                                   "fp16 parts overflowed) or the operands hold inf / NaN")
-            return Y
-        ws_bytes = L.gcn_gemm_xw256_b3_workspace_bytes()
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=X.device)
-        rc = L.gcn_gemm_xw256_f32_b3(X.data_ptr(), X.stride(0),
-                                     rows.data_ptr() if rows is not None else None,
-                                     W.data_ptr(), W.stride(0), Y.data_ptr(), Y.stride(0), m_out,
-                                     y_absmax.data_ptr() if y_absmax is not None else None,
-                                     ep, ws.data_ptr(), ws_bytes, stream)
-    _native.check(rc, "gcn_gemm_xw256_f32_b3")
-    return Y
-
-
-def gemm_bf16(X, W, bias=None, relu=False, dropout_p=0.0, seed=0, row_base=0, mask_src=None,
-              mask_rows=None, mask_scale=1.0):
-    """X[M,K] · W[K,N] for bf16 storage through the streaming MFMA kernel (C-ABI gcn_gemm_xw_bf16;
-    (K, N) in {(128,128), (128,256), (256,128)} — config C5's layers are 128 -> 128).
-    `bias` / `relu` / `dropout_p` / `seed`: the layer's FORWARD epilogue on the fp32 accumulators
-    before the rounding to bf16 (same Philox keep function as the SpMM epilogue) — for a layer
-    evaluated as (Â·X)·W + b.  `mask_src` (bf16 [*, N], read at row mask_rows[r] — an int32 device
-    list — or r for output row r): the store becomes mask_src > 0 ? y * mask_scale : 0, the backward
-    of a fused ReLU / dropout epilogue in the grad_input GEMM's own store (excludes the forward
-    epilogue).  None if the operands do not fit (the caller then uses torch.mm)."""
-    if (X.dtype != torch.bfloat16 or W.dtype != torch.bfloat16 or not X.is_cuda or X.dim() != 2
-            or W.dim() != 2 or X.shape[1] != W.shape[0] or X.shape[0] == 0 or X.stride(1) != 1
-            or W.stride(1) != 1 or X.stride(0) % 8 or X.data_ptr() % 16):
-        return None
-    L = _native.lib()
-    K, N = W.shape
-    ws_bytes = L.gcn_gemm_bf16_workspace_bytes(K, N)
-    if ws_bytes == 0:
-        return None
-    ep = bias32 = None
-    if mask_src is not None:
-        if (bias is not None or relu or dropout_p > 0.0 or mask_src.dtype != torch.bfloat16
-                or mask_src.dim() != 2 or mask_src.shape[1] != N or mask_src.stride(1) != 1
-                or mask_src.stride(0) % 8 or mask_src.data_ptr() % 16 or mask_src.device != X.device):
-            return None
-        if mask_rows is not None and (mask_rows.dtype != torch.int32 or not mask_rows.is_contiguous()
-                                      or mask_rows.device != X.device or mask_rows.numel() < X.shape[0]):
-            raise RuntimeError("gemm_bf16: mask_rows must be a contiguous int32 device list, one entry per output row")
-        ep = _native.GcnGemmEpilogue(None, 0, 0.0, 0, None, mask_src.data_ptr(), mask_src.stride(0),
-                                     float(mask_scale), mask_rows.data_ptr() if mask_rows is not None else None, 0)
-    elif bias is not None or relu or dropout_p > 0.0:
-        if bias is not None:
-            if bias.numel() != N or bias.device != X.device:
-                return None
-            bias32 = bias.detach().to(torch.float32).contiguous()     # (kept alive past the launch)
-        seed_dev = None
-        if isinstance(seed, torch.Tensor):       # device-resident seed (hipGraph capture)
-            seed_dev, seed = seed.data_ptr(), 0
-        ep = _native.GcnGemmEpilogue(bias32.data_ptr() if bias32 is not None else None, int(bool(relu)),
-                                     float(dropout_p), int(seed) & 0xFFFFFFFFFFFFFFFF, seed_dev, None, 0, 1.0, None,
-                                     int(row_base))
-    Y = torch.empty((X.shape[0], N), dtype=torch.bfloat16, device=X.device)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=X.device)
-    with torch.cuda.device(X.device):
-        rc = L.gcn_gemm_xw_bf16(X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0), Y.data_ptr(),
-                                Y.stride(0), X.shape[0], K, N, ep, ws.data_ptr(), ws_bytes,
-                                torch.cuda.current_stream().cuda_stream)
-    _native.check(rc, "gcn_gemm_xw_bf16")
-    return Y
-
-
-def layer_gemm_reassociable(x, weight, bias):
-    """Can `epilogue((A·x)·W + b)` run with the epilogue in a hand-written GEMM's store?  fp32
-    256 -> 256 (gcn_gemm_xw256_f32_h2) or bf16 storage at the streaming kernel's shapes with
-    Fin <= Fout (the product A·x then is no wider than A·(x·W))."""
-    if x.dim() != 2 or not x.is_cuda or x.stride(1) != 1 or weight.dim() != 2 or x.dtype != weight.dtype:
-        return False
-    if x.dtype == torch.float32:
-        return (_gemm_scheme != "exact" and tuple(weight.shape) == (256, 256) and x.shape[1] == 256
-                and (bias is None or (bias.dtype == torch.float32 and bias.is_contiguous())))
-    if x.dtype == torch.bfloat16:
-        return (tuple(weight.shape) in ((128, 128), (128, 256)) and x.shape[1] == weight.shape[0]
-                and weight.stride(1) == 1)
-    return False
-
-
-def layer_gemm(z, weight, z_bound=None, y_absmax=None, bias=None, relu=False, dropout_p=0.0, seed=0,
-               row_base=0, keep_bits_out=None):
-    """epilogue(z·W + b) through the kernel layer_gemm_reassociable() promised (None if it declines)."""
-    if z.dtype == torch.float32:
-        return gemm_xw256(z, weight, z_bound, y_absmax, bias=bias, relu=relu, dropout_p=dropout_p,
-                          seed=seed, row_base=row_base, keep_bits_out=keep_bits_out)
-    return gemm_bf16(z, weight, bias=bias, relu=relu, dropout_p=dropout_p, seed=seed, row_base=row_base)
-
-
-_identity_lists = {}
-
-
-def padded_row_list(rows):
-    """int32 copy of a row-index list, padded to a multiple of 16 entries by repeating its last
-    entry (what gcn_gemm_atg256_f32 expects: the 16 indices of a step are one scalar load)."""
-    r = rows.to(torch.int32)
-    pad = (-r.numel()) % 16
-    if pad and r.numel():
-        r = torch.cat([r, r[-1:].expand(pad)])
-    return r.contiguous()
-
-
-def _identity_list(n, device):
-    """0, 1, …, n-1 (padded) — cached per device, grown on demand."""
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    have = _identity_lists.get(key)
-    need = (n + 15) // 16 * 16
-    if have is None or have.numel() < need:
-        have = _identity_lists[key] = torch.arange(need, dtype=torch.int32, device=device).clamp_(max=max(n - 1, 0))
-        have._n = n
-    if getattr(have, "_n", None) != n:       # the clamp of the padding depends on n
-        have = torch.arange(need, dtype=torch.int32, device=device).clamp_(max=max(n - 1, 0))
-        have._n = n
-        _identity_lists[key] = have
-    return have
-
-
-def weight_grad_rows(A, G, rows_a=None, rows_g=None, a_bound=None, g_bound=None, n_list=None, colsum_g=False):
-    """Σ_r A[rows_a[r]]ᵀ ⊗ G[rows_g[r]] through the gather-fused MFMA kernels: the weight gradient
-    `inputᵀ · grad_support` over a LIST of rows, without compacting either operand first.
-    fp32 [*, 256] x [*, 256] (C-ABI gcn_gemm_atg256_f32_b3: three bf16 parts, fp32-equivalent — or
-    gcn_gemm_atg256_f32, the scaled two-part fp16 scheme, under set_gemm_scheme("h2")) or bf16
-    storage [*, 128] x [*, 128] (C-ABI gcn_gemm_atg_bf16: fp32 accumulation, result rounded once
-    to bf16).  rows_*: int32 device index lists or None (= all rows, in order).  A list may be
-    longer than `n_list` (padding to a multiple of 16, padded_row_list()); unpadded lists are
-    padded here.  *_bound (fp32 only): DEVICE float [1] upper bounds of max|A|, max|G| (computed
-    here by a reduction pass over the listed rows when missing).  None if the operands do not fit
-    a kernel.
-    colsum_g=True (fp32, default scheme): returns (grad_w, Σ_r G[rows_g[r]] as fp32 [256]) — the layer's bias
-    gradient from the rows the kernel loads anyway (C-ABI gcn_gemm_atg256_f32_b3_colsum); None where that
-    form does not exist (the caller then sums G itself)."""
-    bf16 = A.dtype == torch.bfloat16 and G.dtype == torch.bfloat16
-    if colsum_g and (bf16 or _gemm_scheme != "bf16x3"):
-        return None
-    if bf16:
-        if (not A.is_cuda or A.dim() != 2 or G.dim() != 2 or A.stride(1) != 1 or G.stride(1) != 1
-                or A.stride(0) % 2 or G.stride(0) % 2 or A.data_ptr() % 4 or G.data_ptr() % 4
-                or _native.lib().gcn_gemm_atg_bf16_workspace_bytes(16, A.shape[1], G.shape[1]) == 0):
-            return None
-    elif (_gemm_scheme == "exact" or A.dtype != torch.float32 or G.dtype != torch.float32 or not A.is_cuda
-            or A.dim() != 2 or G.dim() != 2 or A.shape[1] != 256 or G.shape[1] != 256 or A.stride(1) != 1
-            or G.stride(1) != 1 or A.stride(0) % 4 or G.stride(0) % 4 or A.data_ptr() % 16 or G.data_ptr() % 16):
-        return None
-    if n_list is None:
-        n_a = rows_a.numel() if rows_a is not None else A.shape[0]
-        n_g = rows_g.numel() if rows_g is not None else G.shape[0]
-        if n_a != n_g:
-            raise RuntimeError("weight_grad_rows: the two operands list different numbers of rows")
-        n_list = n_a
-    if n_list == 0:
-        zero = torch.zeros((A.shape[1], G.shape[1]), dtype=A.dtype, device=A.device)
-        return (zero, torch.zeros(G.shape[1], dtype=torch.float32, device=A.device)) if colsum_g else zero
-    lists = []
-    for r, t in ((rows_a, A), (rows_g, G)):
-        if r is None:
-            if t.shape[0] < n_list:
-                raise RuntimeError("weight_grad_rows: operand has fewer rows than n_list")
-            r = _identity_list(n_list, A.device)
-        elif r.dtype != torch.int32 or not r.is_contiguous() or r.device != A.device:
-            raise RuntimeError("weight_grad_rows: row lists must be contiguous int32 device tensors")
-        elif r.numel() < (n_list + 15) // 16 * 16:
-            r = padded_row_list(r[:n_list])
-        lists.append(r)
-    L = _native.lib()
-    if bf16:
-        K, N = A.shape[1], G.shape[1]
-        out = torch.empty((K, N), dtype=torch.float32, device=A.device)
-        ws_bytes = L.gcn_gemm_atg_bf16_workspace_bytes(n_list, K, N)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=A.device)
-        with torch.cuda.device(A.device):
-            rc = L.gcn_gemm_atg_bf16(A.data_ptr(), A.stride(0), lists[0].data_ptr(), G.data_ptr(),
-                                     G.stride(0), lists[1].data_ptr(), n_list, K, N, out.data_ptr(),
-                                     out.stride(0), ws.data_ptr(), ws_bytes,
-                                     torch.cuda.current_stream().cuda_stream)
-        _native.check(rc, "gcn_gemm_atg_bf16")
-        return out.to(torch.bfloat16)
-    out = torch.empty((256, 256), dtype=torch.float32, device=A.device)
-    ws_bytes = L.gcn_gemm_atg256_workspace_bytes(n_list)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=A.device)
-    if colsum_g:
-        cs = torch.empty(256, dtype=torch.float32, device=A.device)
-        with torch.cuda.device(A.device):
-            rc = L.gcn_gemm_atg256_f32_b3_colsum(A.data_ptr(), A.stride(0), lists[0].data_ptr(),
-                                                 G.data_ptr(), G.stride(0), lists[1].data_ptr(), n_list,
-                                                 out.data_ptr(), out.stride(0), cs.data_ptr(), ws.data_ptr(),
-                                                 ws_bytes, torch.cuda.current_stream().cuda_stream)
-        _native.check(rc, "gcn_gemm_atg256_f32_b3_colsum")
-        return out, cs
-    if _gemm_scheme != "h2":            # three bf16 parts: no bounds
-        with torch.cuda.device(A.device):
-            rc = L.gcn_gemm_atg256_f32_b3(A.data_ptr(), A.stride(0), lists[0].data_ptr(),
-                                          G.data_ptr(), G.stride(0), lists[1].data_ptr(), n_list,
-                                          out.data_ptr(), out.stride(0), ws.data_ptr(), ws_bytes,
-                                          torch.cuda.current_stream().cuda_stream)
-        _native.check(rc, "gcn_gemm_atg256_f32_b3")
-        return out
-    # (no bound supplied: a reduction pass — over the LISTED rows only, the others may hold anything)
-    if a_bound is None:
-        src = A.detach()[:n_list] if rows_a is None else A.detach().index_select(0, rows_a[:n_list].long())
-        a_bound = torch.linalg.vector_norm(src, ord=float("inf")).reshape(1)
-    if g_bound is None:
-        src = G.detach()[:n_list] if rows_g is None else G.detach().index_select(0, rows_g[:n_list].long())
-        g_bound = torch.linalg.vector_norm(src, ord=float("inf")).reshape(1)
-    with torch.cuda.device(A.device):
-        rc = L.gcn_gemm_atg256_f32(A.data_ptr(), A.stride(0), lists[0].data_ptr(),
-                                   G.data_ptr(), G.stride(0), lists[1].data_ptr(), n_list,
-                                   a_bound.data_ptr(), g_bound.data_ptr(), out.data_ptr(), out.stride(0),
-                                   ws.data_ptr(), ws_bytes, torch.cuda.current_stream().cuda_stream)
-    _native.check(rc, "gcn_gemm_atg256_f32")
-    return out
-
-
-_gemm_scheme = "bf16x3"
-_bound_check = False
-
-
-def gemm_scheme():
-    """The current scheme of the fp32 256 -> 256 GEMMs (set_gemm_scheme)."""
-    return _gemm_scheme
-
-
-def gemm_handwritten():
-    """Are the 256-wide fp32 GEMMs on the hand-written MFMA kernels (either decomposition)?"""
-    return _gemm_scheme != "exact"
-
-
-def gemm_needs_bounds():
-    """Only the scaled two-part fp16 scheme needs an upper bound of max|operand|."""
-    return _gemm_scheme == "h2"
-
-
-def set_bound_check(enabled):
-    """DEBUG switch: after every scaled GEMM that reports max|Y|, read it on the host (a stream
-    synchronisation) and raise if it is not finite.  The kernels never hide an overflow — a bound
-    that was too small makes y_absmax inf / NaN (its integer maximum keeps those patterns), and a
-    consumer scaled by a non-finite bound stores NaN — so a wrong bound ends in a NaN loss, not in
-    plausible numbers; this switch names the first launch that overflowed."""
-    global _bound_check
-    _bound_check = bool(enabled)
-
-
-
-def set_gemm_scheme(name):
-    """How the fp32 256 -> 256 GEMMs of the layers are evaluated:
-    "bf16x3" (default since round 4): three bf16 parts per operand, six MFMAs per product — a 24-bit
-        significand, the fp32-EQUIVALENT of the reference's `torch.mm` (pygcn/layers.py:33); no
-        scaling, no bounds, fp32's range; forward (with the layer epilogue), grad_input (with the
-        mask) and the gather-fused weight gradients;
-    "h2": the scaled two-part fp16 MFMA kernels (22-bit significand, half the matrix work, 4e-7
-        normwise vs fp64 on well-scaled data) wherever a bound of max|X| is known — opt-in;
-    "exact": no hand-written fp32 GEMM at all — every dense product is `torch.mm` (hipBLASLt's exact
-        fp32 MFMA path, the arithmetic of the reference's `torch.mm(input, self.weight)`,
-        pygcn/layers.py:33) and the layers keep the reference's order Â·(X·W).  The SpMM kernels
-        are the same in all three."""
-    global _gemm_scheme
-    if name not in ("h2", "bf16x3", "exact"):
-        raise RuntimeError("gemm scheme must be 'h2', 'bf16x3' or 'exact'")
-    _gemm_scheme = name
-
-
-_absmax_cache = {}
-
-
-def absmax_cached(t):
-    """max|t| as a DEVICE float tensor [1], computed once per (tensor object, version): for operands
-    that stay constant across steps (the feature matrix).  A few entries per device (an eval-mode
-    forward pass sees every layer's input as "constant": they must not evict each other), each
-    holding a weak reference to the tensor OBJECT — a new tensor that happens to reuse the storage
-    address of a freed one can never inherit its bound (a bound that is too small would overflow
-    the fp16 parts)."""
-    import weakref
-    key = t.device.index if t.device.index is not None else -1
-    live = [e for e in _absmax_cache.get(key, []) if e[0]() is not None]
-    for ref, version, val in live:
-        if ref() is t and version == t._version:
-            return val
-    val = torch.linalg.vector_norm(t.detach(), ord=float("inf")).float().reshape(1)
-    _absmax_cache[key] = live[-3:] + [(weakref.ref(t), t._version, val)]
-    return val
-
-
-_absmax_known = {}
-
-
-def remember_absmax(t, value):
-    """Record max|t| (a DEVICE float [1] a kernel produced as a side result, e.g. the GEMM's
-    y_absmax) for the tensor OBJECT t at its current version, so that the next layer's GEMM needs
-    no reduction pass over t.  A few entries per device; weak references, like absmax_cached."""
-    import weakref
-    key = t.device.index if t.device.index is not None else -1
-    known = [e for e in _absmax_known.get(key, []) if e[0]() is not None][-3:]
-    known.append((weakref.ref(t), t._version, value))
-    _absmax_known[key] = known
-
-
-def known_absmax(t):
-    """The bound remember_absmax() recorded for this tensor object and version, or None."""
-    key = t.device.index if t.device.index is not None else -1
-    for ref, version, value in _absmax_known.get(key, ()):
-        if ref() is t and version == t._version:
-            return value
-    return None
-
-
-def _dense_forward(input, weight, x_bound=None, y_absmax=None):
-    out = gemm_xw256(input, weight, x_bound, y_absmax)
-    if out is None and y_absmax is None:
-        out = gemm_bf16(input, weight)
-    if out is None:
-        out = torch.mm(input, weight)
-        if y_absmax is not None:
-            y_absmax.copy_(out.detach().abs().max())
-    return out
-
-
-
-
-def _weight_grad(input, grad, a_bound=None, g_bound=None):
-    """inputᵀ · grad: the hand-written MFMA kernel for 256-wide fp32 layers — always under the
-    three-part bf16 scheme; under "h2" when the caller knows bounds of both operands' maxima (the
-    scaling needs them; two reduction passes over [N, 256] tensors would cost what the kernel saves)
-    — otherwise hipBLASLt with the reduction over the graph's vertices cut into K_SPLIT slabs."""
-    if (_gemm_scheme == "bf16x3" and input.dtype == torch.float32) or \
-            (a_bound is not None and g_bound is not None and _gemm_scheme == "h2") or \
-            (input.dtype == torch.bfloat16 and grad.dtype == torch.bfloat16 and input.is_cuda):
-        out = weight_grad_rows(input, grad, a_bound=a_bound, g_bound=g_bound)
-        if out is not None:
-            return out
-    n, b = input.shape[0], K_SPLIT
-    if n >= MIN_ROWS and input.is_contiguous() and grad.is_contiguous():
-        m = n // b * b
-        grad_w = torch.bmm(input[:m].view(b, m // b, -1).transpose(1, 2),
-                           grad[:m].view(b, m // b, -1)).sum(0)
-        if m < n:
-            grad_w = grad_w + torch.mm(input[m:].t(), grad[m:])
-        return grad_w
-    return torch.mm(input.t(), grad)
-
-
-def _dense_grads(input, weight, grad, need_in, need_w, rows=None):
-    """(grad_input, grad_weight) of `input @ weight`.  `rows` (int64 indices, sorted) names the
-    only rows of `grad` that are non-zero: both GEMMs then run on those rows alone — zero rows
-    add nothing to inputᵀ·grad and give zero rows of grad·weightᵀ."""
-    grad_in = grad_w = None
-    if rows is not None:
-        grad = grad.index_select(0, rows)
-        if need_w:
-            grad_w = _weight_grad(input.index_select(0, rows), grad)
-        if need_in:
-            part = gemm_xw256(grad, weight.t().contiguous())
-            if part is None:
-                part = gemm_bf16(grad, weight.t().contiguous())
-            if part is None:
-                part = torch.mm(grad, weight.t())
-            grad_in = torch.zeros((input.shape[0], weight.shape[0]), dtype=part.dtype,
-                                  device=part.device)
-            grad_in.index_copy_(0, rows, part)
-        return grad_in, grad_w
-    if need_in:
-        y_max = torch.zeros(1, dtype=torch.float32, device=grad.device) \
-            if (grad.is_cuda and grad.dtype == torch.float32) else None
-        grad_in = gemm_xw256(grad, weight.t().contiguous(), None, y_max)
-        if grad_in is not None and y_max is not None and _gemm_scheme != "exact":
-            remember_absmax(grad_in, y_max)      # (the layer below bounds its masked gradient by it)
-        if grad_in is None:
-            grad_in = gemm_bf16(grad, weight.t().contiguous())
-        if grad_in is None:
-            grad_in = torch.mm(grad, weight.t())
-    if need_w:
-        grad_w = _weight_grad(input, grad)
-    return grad_in, grad_w
-
-
-class DenseMMFunction(torch.autograd.Function):
-    """`torch.mm(input, weight)` (reference pygcn/layers.py:33) with a K-split weight gradient.
-
-    grad_W = inputᵀ · grad is a [Fin, N]·[N, Fout] GEMM whose reduction runs over the N graph
-    vertices (10⁷ at config C4).  hipBLASLt answers that shape with a stream-K kernel at 21.5 ms;
-    cutting N into 128 slabs, one batched GEMM over the slabs and a sum of the 128 small partial
-    products takes 8.7 ms on MI355X (tools/gemm_probe.py) and is at least as accurate (shorter
-    fp32 accumulation chains).
-
-    Forward and grad_input use the hand-written MFMA kernels when the layer is 256 -> 256 fp32
-    (gemm_xw256: 5.2 ms vs hipBLASLt 9.95 ms at N = 10⁷) or one of the bf16 shapes of gemm_bf16,
-    torch.mm otherwise.  (The one-node training path, pygcn_amd/fused.py, forms the weight
-    gradient with the gather-fused kernel weight_grad_rows instead.)"""
-
-    K_SPLIT = K_SPLIT
-    MIN_ROWS = MIN_ROWS
-
-    @staticmethod
-    def forward(ctx, input, weight):
-        ctx.save_for_backward(input, weight)
-        bound = known_absmax(input) if (input.is_cuda and input.dtype == torch.float32) else None
-        return _dense_forward(input, weight, bound)
-
-    @staticmethod
-    def backward(ctx, grad):
-        input, weight = ctx.saved_tensors
-        return _dense_grads(input, weight, grad, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-
-
 _row_compaction = False
 
 
@@ -1108,7 +575,7 @@ class GraphConvFunction(torch.autograd.Function):
             grad_w = grad_in = None
             if need_w:
                 grad_w = weight_grad_rows(input, grad_sup, rs.rows2_padded, None, ctx.x_bound, gs_bound,
-                                          n_list=rs.n2) if (f32 and _gemm_scheme != "exact" and
+                                          n_list=rs.n2) if (f32 and gemm_handwritten() and
                                                             (ctx.x_bound is not None or not gemm_needs_bounds())) else None
                 if grad_w is None:
                     grad_w = _weight_grad(input.index_select(0, rs.rows2), grad_sup)

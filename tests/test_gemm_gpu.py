@@ -19,8 +19,8 @@ def dev():
 
 def _run(scheme, X, W, bound=None):
     """Y through one of the two kernels; for "h2" the bound defaults to the exact max|X|."""
-    from pygcn_amd import spmm as S
-    from pygcn_amd.spmm import gemm_xw256
+    from pygcn_amd import gemm as S
+    from pygcn_amd.gemm import gemm_xw256
     before = S.gemm_scheme()
     S.set_gemm_scheme(scheme)
     try:
@@ -41,7 +41,7 @@ def test_three_part_pipeline_equals_the_round_one_kernel_bitwise(dev, M):
     ragged tile, several tiles, and a cross-tile prefetch.  Contiguous rows take gemm_xw256_s16_kernel
     (16x16x32 MFMAs, K chunks of 32: another fp32 summation order, stores under the next tile's MFMAs):
     held against the listed result to fp32 rounding of the ROW's scale, and bit-for-bit repeatable."""
-    from pygcn_amd import _native, spmm as S
+    from pygcn_amd import _native, gemm as S
     L = _native.lib()
     g = torch.Generator(device=dev).manual_seed(M)
     X = torch.randn(M, 256, generator=g, device=dev) * (10 ** (4 * torch.rand(M, 1, generator=g, device=dev) - 2))
@@ -159,7 +159,7 @@ def test_gemm_precision_at_the_edges_of_fp32(dev, scheme):
 def test_gemm_output_maximum_side_channel(dev, gemm_scheme):
     """gcn_gemm_xw256_f32_h2 reports max|Y| (the next layer's bound) without a pass over Y; and
     without a caller-supplied bound the wrapper computes max|X| itself."""
-    from pygcn_amd.spmm import gemm_xw256
+    from pygcn_amd.gemm import gemm_xw256
     X = torch.randn(3000, 256, device=dev) * 3
     W = torch.randn(256, 256, device=dev)
     ymax = torch.zeros(1, device=dev)
@@ -169,7 +169,7 @@ def test_gemm_output_maximum_side_channel(dev, gemm_scheme):
 
 
 def test_gemm_declines_other_shapes(dev):
-    from pygcn_amd.spmm import gemm_xw256
+    from pygcn_amd.gemm import gemm_xw256
     assert gemm_xw256(torch.randn(10, 128, device=dev), torch.randn(128, 256, device=dev)) is None
     assert gemm_xw256(torch.randn(10, 256, device=dev).bfloat16(),
                       torch.randn(256, 256, device=dev).bfloat16()) is None
@@ -212,7 +212,7 @@ def test_layer_256_to_256_through_custom_gemm(oracle, dev, gemm_scheme):
 def test_weight_gradient_over_row_lists_matches_fp64(dev, M, gemm_scheme):
     """gcn_gemm_atg256_f32: Σ_r A[ra[r]]ᵀ ⊗ G[rg[r]] with and without row lists (the weight
     gradient of pygcn/layers.py:33 over the rows on which the gradient can be non-zero)."""
-    from pygcn_amd.spmm import weight_grad_rows
+    from pygcn_amd.gemm import weight_grad_rows
     gen = torch.Generator(device=dev).manual_seed(M)
     n_a, n_g = 3 * M + 5, 2 * M + 3
     A = torch.randn(n_a, 256, generator=gen, device=dev) * 3
@@ -245,7 +245,7 @@ def test_weight_gradient_with_the_bias_gradient_as_a_side_result(dev, M):
     """gcn_gemm_atg256_f32_b3_colsum: the weight gradient unchanged (same bits) and Σ_r G[rg[r]] — the layer's
     bias gradient (pygcn/layers.py:36) — from the rows the kernel loads anyway: against a float64 sum, with and
     without row lists, poisoned unlisted rows, lists that end inside a 32-row super-step and a 16-entry pad."""
-    from pygcn_amd import spmm as S
+    from pygcn_amd import gemm as S
     gen = torch.Generator(device=dev).manual_seed(M + 7)
     n_g = 2 * M + 3
     A = torch.randn(M, 256, generator=gen, device=dev)
@@ -275,7 +275,7 @@ def test_weight_gradient_with_the_bias_gradient_as_a_side_result(dev, M):
 
 
 def test_weight_gradient_degenerate_lists(dev):
-    from pygcn_amd.spmm import weight_grad_rows
+    from pygcn_amd.gemm import weight_grad_rows
     A, G = torch.randn(10, 256, device=dev), torch.randn(10, 256, device=dev)
     empty = torch.empty(0, dtype=torch.int32, device=dev)
     assert bool((weight_grad_rows(A, G, empty, empty) == 0).all())
@@ -286,7 +286,7 @@ def test_weight_gradient_degenerate_lists(dev):
 
 def test_gemm_with_row_list(dev, gemm_scheme):
     """gcn_gemm_xw256_f32_h2 with x_rows: output row r = X[rows[r]] · W, unlisted rows never read."""
-    from pygcn_amd.spmm import gemm_xw256
+    from pygcn_amd.gemm import gemm_xw256
     X = torch.randn(5000, 256, device=dev)
     W = torch.randn(256, 256, device=dev)
     rows = torch.randperm(5000, device=dev)[:1237].to(torch.int32)
@@ -309,7 +309,7 @@ def test_bf16_gemm_matches_fp32_on_rounded_inputs(dev, K, N, M):
     """gcn_gemm_xw_bf16 (config C5: 128 -> 128): bf16 products are exact in fp32, so against an fp64
     product of the same bf16 inputs only the fp32 accumulation and the final rounding to bf16
     (2^-9 relative) differ."""
-    from pygcn_amd.spmm import gemm_bf16
+    from pygcn_amd.gemm import gemm_bf16
     gen = torch.Generator(device=dev).manual_seed(K + N + M)
     X = torch.randn(M, K, generator=gen, device=dev).bfloat16()
     W = (torch.randn(K, N, generator=gen, device=dev) * 0.2).bfloat16()
@@ -331,7 +331,7 @@ def test_bf16_gemm_matches_fp32_on_rounded_inputs(dev, K, N, M):
 def test_gemm_with_fused_relu_dropout_mask(dev, gemm_scheme):
     """mask_src: y = mask_src[input row] > 0 ? y * scale : 0 in the GEMM's own store (the backward
     of the fused ReLU / dropout epilogue on the grad_input GEMM), with and without a row list."""
-    from pygcn_amd.spmm import gemm_xw256
+    from pygcn_amd.gemm import gemm_xw256
     gen = torch.Generator(device=dev).manual_seed(4)
     X = torch.randn(4000, 256, generator=gen, device=dev)
     H = torch.randn(4000, 256, generator=gen, device=dev).clamp_min(0) * (torch.rand(4000, 256, generator=gen, device=dev) > 0.5)
@@ -355,8 +355,8 @@ def test_keep_bits_carry_the_backward_mask(dev, M, p):
     """gcn_gemm_epilogue.keep_bits_out / mask_bits (ABI 25): the forward launch writes `out > 0` as one bit per
     element, the grad_input launch masks from those bits — the SAME bits as masking from the fp32 activations,
     with and without a mask row list; launches that cannot take the contiguous-row kernel read mask_src."""
-    from pygcn_amd import spmm as S
-    from pygcn_amd.spmm import gemm_xw256
+    from pygcn_amd import gemm as S
+    from pygcn_amd.gemm import gemm_xw256
     gen = torch.Generator(device=dev).manual_seed(M + int(10 * p))
     X = torch.randn(M, 256, generator=gen, device=dev)
     W = torch.randn(256, 256, generator=gen, device=dev) * 0.1
@@ -393,7 +393,7 @@ def test_gemm_forward_epilogue_matches_the_spmm_epilogue(dev, p, gemm_scheme):
     same values — and the SAME Philox keep bits for a given (seed, row, column) — as the SpMM
     epilogue applied to the plain product (checked through an identity adjacency)."""
     from pygcn_amd import CSRGraph, spmm_csr
-    from pygcn_amd.spmm import gemm_xw256
+    from pygcn_amd.gemm import gemm_xw256
     gen = torch.Generator(device=dev).manual_seed(12)
     M = 3001
     X = torch.randn(M, 256, generator=gen, device=dev)
@@ -402,7 +402,7 @@ def test_gemm_forward_epilogue_matches_the_spmm_epilogue(dev, p, gemm_scheme):
     b = X.abs().max().reshape(1)
     # (three-part scheme: dropout at p != 1/2 has no instantiation of the contiguous-row kernel and
     #  runs the listed rows' one — take the plain product from the same kernel)
-    from pygcn_amd import spmm as S
+    from pygcn_amd import gemm as S
     other = S.gemm_scheme() == "bf16x3" and p not in (0.0, 0.5)
     plain = gemm_xw256(X, W, x_bound=b, rows=torch.arange(M, device=dev, dtype=torch.int32) if other else None)
     ident = CSRGraph(torch.arange(M + 1, device=dev, dtype=torch.int32),
@@ -436,7 +436,7 @@ def test_bf16_gemm_forward_epilogue(dev, K, N, p):
     once; the keep bits are those of the SpMM epilogue for the same (seed, row, column) — read off
     an identity-adjacency product of an all-ones operand."""
     from pygcn_amd import CSRGraph, spmm_csr
-    from pygcn_amd.spmm import gemm_bf16
+    from pygcn_amd.gemm import gemm_bf16
     gen = torch.Generator(device=dev).manual_seed(K + N)
     M = 2777
     X = torch.randn(M, K, generator=gen, device=dev).bfloat16()
@@ -471,8 +471,8 @@ def test_a_bound_that_is_too_small_is_never_silent(dev, h2_scheme):
     too small overflows the fp16 parts; that must surface — y_absmax becomes non-finite (its
     integer maximum keeps inf / NaN patterns), a consumer scaled by such a bound stores NaN, and
     the debug switch names the launch — never plausible-looking numbers."""
-    import pygcn_amd.spmm as S
-    from pygcn_amd.spmm import gemm_xw256, weight_grad_rows
+    import pygcn_amd.gemm as S
+    from pygcn_amd.gemm import gemm_xw256, weight_grad_rows
     torch.manual_seed(0)
     M = 4096
     X = torch.randn(M, 256, device=dev)
@@ -506,7 +506,7 @@ def test_bf16_weight_gradient_over_row_lists(dev, m, listed):
     """gcn_gemm_atg_bf16 (config C5's weight gradients): Σ_r A[ra[r]]ᵀ ⊗ G[rg[r]] for bf16 [*, 128]
     operands, fp32 accumulation — against an fp64 product of the same bf16-rounded values, with
     and without row lists (gathers fused into the loads), odd list lengths, duplicates."""
-    from pygcn_amd.spmm import padded_row_list, weight_grad_rows
+    from pygcn_amd.gemm import padded_row_list, weight_grad_rows
     torch.manual_seed(m)
     n = max(m, 64) * 3
     A = torch.randn(n, 128, device=dev).bfloat16()
@@ -535,7 +535,7 @@ def test_bf16_gemm_with_backward_mask_in_the_store(dev):
     """gcn_gemm_xw_bf16 with `mask_src` / `mask_rows`: the backward of a fused ReLU / dropout epilogue
     (y = mask > 0 ? y * scale : 0) in the grad_input GEMM's own store at bf16 (config C5), the mask
     read through a row list — against the unfused composition on the same bf16 values."""
-    from pygcn_amd.spmm import gemm_bf16
+    from pygcn_amd.gemm import gemm_bf16
     torch.manual_seed(5)
     M, n = 7001, 30000
     X = torch.randn(M, 128, device=dev).bfloat16()
@@ -567,7 +567,7 @@ def test_bf16_gemm_pipeline_across_tiles(dev, M):
     every store variant must repeat its bits across launches, the masked forms must equal the
     plain product masked afterwards (scale 1: the same rounding), the row-list form the
     own-row form, and the plain product an fp64 product of the same bf16 values."""
-    from pygcn_amd.spmm import gemm_bf16
+    from pygcn_amd.gemm import gemm_bf16
     g = torch.Generator(device=dev).manual_seed(M)
     X = torch.randn(M, 128, device=dev, generator=g).bfloat16()
     W = (torch.randn(128, 128, device=dev, generator=g) * 0.1).bfloat16()
@@ -602,7 +602,7 @@ def test_bf16_gemm_mask_at_the_wider_shapes(dev, K, N):
     """The shapes whose accumulators leave no registers for a tile's whole mask fetch it per column
     block in the store section: same result as the plain product masked afterwards (scale 1), with
     and without a row list, ragged height, repeatable."""
-    from pygcn_amd.spmm import gemm_bf16
+    from pygcn_amd.gemm import gemm_bf16
     M = 70_003
     g = torch.Generator(device=dev).manual_seed(K + N)
     X = torch.randn(M, K, device=dev, generator=g).bfloat16()
@@ -624,7 +624,7 @@ def test_dma_pipeline_is_deterministic_across_tiles_and_launches(dev, gemm_schem
     Many launches over inputs that give every persistent workgroup several tiles (cross-tile
     prefetch), a ragged last tile, a row list and both epilogues — all launches must store the same
     bits, and the plain result must match an fp64 product."""
-    from pygcn_amd.spmm import gemm_xw256
+    from pygcn_amd.gemm import gemm_xw256
     torch.manual_seed(11)
     for M in (300_007, 70_001, 257):
         X = torch.randn(M, 256, device=dev)

@@ -27,6 +27,22 @@ def test_library_exports_every_declared_symbol():
         assert int(re.search(rf"#define {name}\s+(\d+)", hdr).group(1)) == getattr(_native, name)
 
 
+def test_signature_table_has_the_header_parameter_counts():
+    """Every function the header declares has as many `argtypes` in _native.SIGNATURES as its
+    declaration has parameters (`(void)` = 0): a name bound without its signature would be called
+    with ctypes' default `int` conversion, device addresses and int64_t sizes cut to 32 bits.
+    Needs neither the library nor a GPU."""
+    hdr = open(os.path.join(ROOT, "include", "gcn_spmm.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    decls = re.findall(r"^[A-Za-z_][\w \*]*?\b(gcn_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr, flags=re.M)
+    counts = {name: 0 if params.strip() == "void" else len(params.split(",")) for name, params in decls}
+    assert set(counts) == set(_native.SIGNATURES), set(counts) ^ set(_native.SIGNATURES)
+    assert len(decls) == len(counts)          # (each declared once)
+    for name, (restype, argtypes) in _native.SIGNATURES.items():
+        assert restype is not None and isinstance(argtypes, list), name
+        assert len(argtypes) == counts[name], (name, len(argtypes), counts[name])
+
+
 def test_plan_struct_layout_matches_header():
     # 3*8 + 8 + 4 + 4 + 2*8 + (8+8) + (8+8+8) + (8+8+8) bytes, natural alignment, no padding holes
     assert ctypes.sizeof(_native.GcnCsrPlan) == 120
@@ -361,3 +377,27 @@ def test_package_ships_its_own_cora_fixture():
         if name.endswith(".py"):
             src = open(os.path.join(pkg, name)).read()
             assert '"tests"' not in src and "from tests" not in src and "import tests" not in src, name
+
+
+def test_seed_fields_and_absmax_cache_of_the_gemm_wrappers():
+    """Host logic of pygcn_amd/gemm.py that needs no device: a tensor seed is validated in ONE place
+    (spmm_csr's rule, now for the GEMM epilogues too), and the two kinds of max|t| entry — computed
+    (absmax_cached) and recorded (remember_absmax / known_absmax) — share one cache without evicting
+    each other; both are bound to the tensor object AND its version."""
+    from pygcn_amd import gemm
+    cpu = torch.device("cpu")
+    assert gemm._seed_fields(-1, cpu, "x") == (2 ** 64 - 1, None)
+    t = torch.zeros(1, dtype=torch.int64)
+    assert gemm._seed_fields(t, cpu, "x") == (0, t.data_ptr())
+    for bad in (torch.zeros(2, dtype=torch.int64), torch.zeros(1, dtype=torch.int32)):
+        with pytest.raises(RuntimeError, match="tensor seed"):
+            gemm._seed_fields(bad, cpu, "x")
+    tensors = [torch.full((3, 2), float(k + 1)) for k in range(4)]
+    first = [gemm.absmax_cached(x) for x in tensors]
+    for k, x in enumerate(tensors):                       # (four recorded entries on top of four computed ones)
+        gemm.remember_absmax(x, torch.tensor([10.0 + k]))
+    assert all(gemm.absmax_cached(x) is v for x, v in zip(tensors, first))
+    assert [gemm.known_absmax(x).item() for x in tensors] == [10.0, 11.0, 12.0, 13.0]
+    assert gemm.known_absmax(torch.ones(3, 2)) is None
+    tensors[0].add_(1.0)                                  # a new version: neither entry applies
+    assert gemm.known_absmax(tensors[0]) is None and gemm.absmax_cached(tensors[0]).item() == 2.0

@@ -89,7 +89,7 @@ def _pack_keep_bits(pos):
 def test_fp32_gemm_full_height(dev, keep):
     """gemm_xw256 (default scheme, contiguous rows: gemm_xw256_s16_kernel) at M = 2^24 + 37: plain; the
     forward epilogue bias + ReLU + dropout 1/2 with keep bits; the grad_input form masked from those bits."""
-    from pygcn_amd import spmm as S
+    from pygcn_amd import gemm as S
     assert S.gemm_scheme() == "bf16x3"
     gen = torch.Generator(device=dev).manual_seed(2024)
     X = _scaled_rows(M32, 256, gen, dev)
@@ -142,7 +142,7 @@ def test_fp32_gemm_full_height(dev, keep):
 def test_fp32_gemm_row_list_and_h2_full_height(dev, scheme):
     """gemm_xw256 through a list of 10^6 random rows of a 2^24 + 37-row operand (round 3's listed-row
     pipeline; every output row checked), and the contiguous launch at full height under each scheme."""
-    from pygcn_amd import spmm as S
+    from pygcn_amd import gemm as S
     gen = torch.Generator(device=dev).manual_seed(77)
     X = _scaled_rows(M32, 256, gen, dev)
     W = torch.randn(256, 256, generator=gen, device=dev)
@@ -169,7 +169,7 @@ def test_fp32_gemm_row_list_and_h2_full_height(dev, scheme):
 def test_bf16_gemm_full_height(dev, keep):
     """gemm_bf16 128 -> 128 at M = 2^25 + 37 (more than 2^32 elements): plain, the forward epilogue at
     p = 1/2, and the mask_src backward — against float64 on the same bf16 values."""
-    from pygcn_amd.spmm import gemm_bf16
+    from pygcn_amd.gemm import gemm_bf16
     gen = torch.Generator(device=dev).manual_seed(2025)
     X = torch.randn(M16, 128, generator=gen, device=dev).bfloat16()
     W = (torch.randn(128, 128, generator=gen, device=dev) * 0.2).bfloat16()
@@ -232,7 +232,7 @@ def _colsum_gate(cs, ref, absref, rel, what):
 
 def test_fp32_weight_gradient_full_height(dev):
     """weight_grad_rows (atg256 b3 with the column sums) over all 10^7 + 13 rows, no list."""
-    from pygcn_amd import spmm as S
+    from pygcn_amd import gemm as S
     assert S.gemm_scheme() == "bf16x3"
     n = 10_000_013
     gen = torch.Generator(device=dev).manual_seed(31)
@@ -248,7 +248,7 @@ def test_fp32_weight_gradient_full_height(dev):
 @pytest.mark.parametrize("scheme", ["bf16x3", "h2"])
 def test_fp32_weight_gradient_row_lists_full_height(dev, scheme):
     """weight_grad_rows over lists of 5·10^6 rows into 1.6·10^7-row operands (gathers past element 2^31)."""
-    from pygcn_amd import spmm as S
+    from pygcn_amd import gemm as S
     n, m = 16_000_000, 5_000_000
     gen = torch.Generator(device=dev).manual_seed(32)
     A = torch.randn(n, 256, generator=gen, device=dev) * 3
@@ -273,7 +273,7 @@ def test_fp32_weight_gradient_row_lists_full_height(dev, scheme):
 
 def test_bf16_weight_gradient_full_height(dev):
     """weight_grad_rows for bf16 [5·10^7, 128] operands (atg_bf16): fp32 accumulation, one rounding to bf16."""
-    from pygcn_amd.spmm import weight_grad_rows
+    from pygcn_amd.gemm import weight_grad_rows
     n = 50_000_000
     gen = torch.Generator(device=dev).manual_seed(33)
     A = torch.randn(n, 128, generator=gen, device=dev).bfloat16()

@@ -246,7 +246,7 @@ def _bf16_worker(rank, world, port, n, n_edges, out_dir):
         smodel = ShardedGCN(model, sg)
         model.train()
         seen = []
-        import pygcn_amd.spmm as S
+        import pygcn_amd.sharded as S       # (the module whose layer function makes the call)
         orig = S.layer_gemm
         S.layer_gemm = lambda *a, **k: (seen.append(a[0].dtype), orig(*a, **k))[1]
         try:

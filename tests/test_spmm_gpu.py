@@ -1167,7 +1167,7 @@ def test_dropout_row_base_gives_a_shard_the_masks_of_the_whole(oracle, dev, F, d
     that passes its first global row draws exactly the masks the single-GPU run draws for those
     rows (SpMM epilogue and both GEMM epilogues; oracle.dropout_keep restates the function)."""
     from pygcn_amd import CSRGraph, spmm_csr
-    from pygcn_amd.spmm import gemm_bf16, gemm_xw256
+    from pygcn_amd.gemm import gemm_bf16, gemm_xw256
     n, base, seed = 700, 123456789012, 0xC0FFEE1234
     eye = CSRGraph(torch.arange(n + 1, dtype=torch.int32, device=dev), torch.arange(n, dtype=torch.int32, device=dev),
                    torch.ones(n, device=dev), (n, n))

@@ -3,7 +3,7 @@ height — fp32 256 x 256 at M = 10^7 (gcn_gemm_atg256_f32) and bf16 128 x 128 a
 (gcn_gemm_atg_bf16) — with the fraction of the HBM roofline (both operands read once)."""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
-from pygcn_amd.spmm import weight_grad_rows
+from pygcn_amd.gemm import weight_grad_rows
 dev = torch.device("cuda:0")
 def t(fn, reps=5):
     fn(); torch.cuda.synchronize()

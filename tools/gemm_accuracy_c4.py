@@ -20,7 +20,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from pygcn_amd import GCN, CSRGraph, fused, spmm as S   # noqa: E402
+from pygcn_amd import GCN, CSRGraph, fused, gemm as S   # noqa: E402
 from pygcn_amd.functional import nll_loss   # noqa: E402
 from pygcn_amd.utils import rmat_graph   # noqa: E402
 

@@ -4,7 +4,7 @@ backward mask through a row list — with the fraction of the HBM roofline each 
 Y once, the mask once where there is one)."""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
-from pygcn_amd.spmm import gemm_bf16
+from pygcn_amd.gemm import gemm_bf16
 dev = torch.device("cuda:0")
 M, F = int(os.environ.get("GEMM_M", 50_000_000)), 128
 X = torch.randn(M, F, device=dev, dtype=torch.bfloat16)

@@ -2,7 +2,7 @@
 in one process (A/B on one box): gcn_gemm_xw256_f32 (3 x bf16) and gcn_gemm_xw256_f32_h2 (2 x fp16)."""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
-from pygcn_amd.spmm import gemm_xw256
+from pygcn_amd.gemm import gemm_xw256
 dev = torch.device("cuda:0")
 for M in (1000, 100003):
     X = torch.randn(M, 256, device=dev) * torch.rand(M, 1, device=dev) * 10

@@ -3,7 +3,7 @@ the torch / hipBLASLt forms they replace, at the bench's backward shapes (|R2| =
 plus the bf16 128 -> 128 GEMM at config C5's height — one process, interleaved rounds."""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
-from pygcn_amd import spmm as S
+from pygcn_amd import gemm as S
 dev = torch.device("cuda:0")
 def t(fn, reps=5):
     fn(); torch.cuda.synchronize()

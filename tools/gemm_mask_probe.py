@@ -2,7 +2,7 @@
 forward epilogue (bias + ReLU + dropout) and with the ReLU / dropout backward mask in its store."""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
-from pygcn_amd.spmm import gemm_xw256
+from pygcn_amd.gemm import gemm_xw256
 dev = torch.device("cuda:0")
 M = int(os.environ.get("GEMM_M", 10_000_000))
 X = torch.randn(M, 256, device=dev); W = torch.randn(256, 256, device=dev) * 0.06

@@ -3,7 +3,7 @@ fp32 256 -> 256 product and three of the forward-epilogue instantiation (bias + 
 M = 10^7, with a bound supplied (no reduction pass in between)."""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
-from pygcn_amd.spmm import gemm_xw256
+from pygcn_amd.gemm import gemm_xw256
 dev = torch.device("cuda:0")
 X = torch.randn(10_000_000, 256, device=dev); W = torch.randn(256, 256, device=dev) * 0.06
 bias = torch.randn(256, device=dev) * 0.1

@@ -10,7 +10,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from pygcn_amd import _native, spmm as S   # noqa: E402
+from pygcn_amd import _native, gemm as S   # noqa: E402
 
 dev = torch.device("cuda:0")
 L = _native.lib()

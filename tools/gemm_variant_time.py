@@ -8,7 +8,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from pygcn_amd import spmm as S   # noqa: E402
+from pygcn_amd import gemm as S   # noqa: E402
 
 dev = torch.device("cuda:0")
 M = int(os.environ.get("GEMM_M", 10_000_000))
