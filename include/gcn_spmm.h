@@ -36,7 +36,7 @@ extern "C" {
 #define GCN_DTYPE_F32  0      /* B, C fp32; fp32 accumulate  (configs C1-C4)                  */
 #define GCN_DTYPE_BF16 1      /* B, C bf16 storage; fp32 values and accumulate (config C5)    */
 
-#define GCN_ABI_VERSION 25
+#define GCN_ABI_VERSION 26
 
 #define GCN_DEFAULT_ITEM_COST   64     /* work units (stored entries + rows) per row-batch item */
 #define GCN_DEFAULT_LONG_THRESH 256    /* rows with more stored entries are chunked             */
@@ -72,7 +72,9 @@ typedef struct gcn_csr_plan {
     const int32_t *long_chunk0;/* [n_long+1] first chunk of every long row                   */
 } gcn_csr_plan;
 
-/* ABI history: 21 = round 2's surface.  25 (round 4, late): new entry point gcn_gemm_atg256_f32_b3_colsum (the
+/* ABI history: 21 = round 2's surface.  26: the ReLU + BatchNorm sweeps gcn_bn_workspace_bytes / gcn_bn_stats /
+ * gcn_bn_apply / gcn_bn_backward_sums / gcn_bn_backward_apply — new entry points only; nothing existing changed.
+ * 25 (round 4, late): new entry point gcn_gemm_atg256_f32_b3_colsum (the
  * weight gradient with the bias gradient Σ G[rows] as a side result); gcn_gemm_atg256_workspace_bytes grew by
  * 1 KiB per workgroup; struct gcn_gemm_epilogue gained keep_bits_out / mask_bits at its END (zero them);
  * nothing else changed.  24 (round 4): new entry points gcn_gemm_xw256_f32_b3 /
@@ -541,6 +543,50 @@ int gcn_rows_pack_values(int dtype, const void *src, int64_t ld, const int64_t *
 int gcn_rows_unpack(int dtype, const uint32_t *bits, const int64_t *offsets, const void *vals, int64_t m,
                     int64_t F, void *dst, int64_t ldd, void *stream);
 int gcn_bits_row_counts(const uint32_t *bits, int64_t m, int64_t words, int32_t *counts, void *stream);
+
+/*
+ * ReLU + training-mode BatchNorm over the rows of a contiguous row-major [n_rows, F] activation —
+ * the fork's live model normalises the output of its first two layers,
+ *     x = self.apply_bn(F.relu(self.gc1(x, adj)))                 reference pygcn/models.py:49,53
+ *     apply_bn: nn.BatchNorm1d(x.size()[1]).cuda()(x)             reference pygcn/models.py:41-45
+ * (a fresh module per call: batch statistics, gamma = 1, beta = 0).  With x = relu ? relu(z) : z:
+ *     mean[f] = mean_r x[r,f]    var[f] = mean_r (x[r,f] - mean[f])^2  (biased, as BatchNorm normalises)
+ *     rstd = 1 / sqrt(var + eps) xhat = (x - mean) * rstd              y = xhat * gamma + beta
+ *     backward, g = dL/dy:       sum_g = sum_r g  (= dbeta)            sum_gxhat = sum_r g * xhat  (= dgamma)
+ *     dx = gamma * rstd * (g - sum_g / n - xhat * sum_gxhat / n)       dz = (relu && z <= 0) ? 0 : dx
+ * as four sweeps: 3 activation-sized streams forward (stats: read z; apply: read z, write y) and 5
+ * backward (sums: read g, z; apply: read g, z, write dz).  ReLU and its backward mask ride in the
+ * loads; xhat is recomputed from z.  relu(NaN) = NaN and the mask passes dx where z is NaN, as torch.
+ * `dtype` (fp32 / bf16) is the storage of z, y, g, dz: the forward arithmetic is fp32, results are
+ * rounded once in the store; mean, var, rstd, gamma, beta, sum_g, sum_gxhat are DEVICE fp32 [F]; gamma
+ * and beta may each be NULL (1 resp. 0).  The reductions carry their running sums in double and add
+ * per-block partial rows in block order (no float atomics): deterministic, and the variance of a
+ * column far from zero survives.
+ * The backward pair works in double: over few rows dx cancels to eps * rstd^2 of its terms, and an
+ * fp32 rounding of mean, rstd or a sum would come out multiplied by the inverse of that (3e-5 of
+ * max|dz| at n_rows = 2).  gcn_bn_backward_sums therefore takes the fp32 `mean` of gcn_bn_stats only as
+ * the centre of its sums, recovers the column's mean, var and rstd = 1 / sqrt(var + eps) to double
+ * precision from z (which it reads anyway), and writes, besides sum_g and sum_gxhat, the DEVICE
+ * double `coef`[4][F] = { mean, rstd, sum_g / n, rstd^2 * sum_r g (x - mean) / n } that
+ * gcn_bn_backward_apply evaluates dx from (NULL: GCN_E_BADARG; 8-byte aligned).
+ * Shape rule of gcn_relu_dropout_backward_colsum: F a multiple of the
+ * 16-byte lane width v (4 fp32 / 8 bf16) with F/v dividing 256; that or n_rows < 2 is GCN_E_BADARG.
+ * Tensors and workspace 16-byte aligned (GCN_E_ALIGN).  dz may alias g.
+ * Scratch of the two reducing calls (0 for a shape outside the rule):
+ *     gcn_bn_workspace_bytes = B * 4 * F * sizeof(double),  B = min(ceil(n_rows / 64), 2048) blocks,
+ *     block b sweeping rows [b * R, min((b + 1) * R, n_rows)) with R = ceil(n_rows / B).
+ * (ABI 26.)
+ */
+size_t gcn_bn_workspace_bytes(int64_t n_rows, int64_t F, int dtype);
+int gcn_bn_stats(int dtype, const void *z, int64_t n_rows, int64_t F, int relu, float eps, float *mean,
+                 float *var, float *rstd, void *workspace, size_t workspace_bytes, void *stream);
+int gcn_bn_apply(int dtype, const void *z, void *y, int64_t n_rows, int64_t F, int relu, const float *mean,
+                 const float *rstd, const float *gamma, const float *beta, void *stream);
+int gcn_bn_backward_sums(int dtype, const void *g, const void *z, int64_t n_rows, int64_t F, int relu, float eps,
+                         const float *mean, float *sum_g, float *sum_gxhat, double *coef, void *workspace,
+                         size_t workspace_bytes, void *stream);
+int gcn_bn_backward_apply(int dtype, const void *g, const void *z, void *dz, int64_t n_rows, int64_t F, int relu,
+                          const float *gamma, const double *coef, void *stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (GCN_SPMM_LIB: an experiment build of the same ABI — tools/build_gemm_variant.sh; never set in product use)
 LIB_PATH = os.environ.get("GCN_SPMM_LIB") or os.path.join(_HERE, "csrc", "libgcn_spmm.so")
 
-GCN_ABI_VERSION = 25
+GCN_ABI_VERSION = 26
 GCN_REDUCE_SUM = 0
 GCN_REDUCE_MAX = 1
 GCN_DEFAULT_ITEM_COST = 64
@@ -108,6 +108,11 @@ SIGNATURES = {
     "gcn_rows_pack_values": (i, [i, p, i64, p, i64, i64, p, p, p]),
     "gcn_rows_unpack": (i, [i, p, p, p, i64, i64, p, i64, p]),
     "gcn_bits_row_counts": (i, [p, i64, i64, p, p]),
+    "gcn_bn_workspace_bytes": (sz, [i64, i64, i]),
+    "gcn_bn_stats": (i, [i, p, i64, i64, i, f32, p, p, p, p, sz, p]),
+    "gcn_bn_apply": (i, [i, p, p, i64, i64, i, p, p, p, p, p]),
+    "gcn_bn_backward_sums": (i, [i, p, p, i64, i64, i, f32, p, p, p, p, p, sz, p]),
+    "gcn_bn_backward_apply": (i, [i, p, p, p, i64, i64, i, p, p, p]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -1,0 +1,474 @@
+// gcn_norm.hip — ReLU + training-mode BatchNorm over a [n_rows, F] activation as four full-height
+// sweeps (gfx950).
+//
+// The reference fork's live model normalises the output of its first two layers,
+//     x = apply_bn(F.relu(gc(x, adj)))          reference pygcn/models.py:49,53
+//     apply_bn = nn.BatchNorm1d(x.size(1)).cuda()(x)                     :41-45
+// i.e. batch statistics over all vertices, per feature column.  With x = relu ? relu(z) : z:
+//     forward   bn_stats_kernel     reads z              -> mean, var (biased), rstd          1 stream
+//               bn_apply_kernel     reads z, writes y    y = (x - mean) * rstd * gamma + beta 2 streams
+//     backward  bn_bwd_sums_kernel  reads g, z           -> sum g, sum g * xhat, coef         2 streams
+//               bn_bwd_apply_kernel reads g, z, writes dz                                     3 streams
+//     dx = gamma * rstd * (g - sum_g / n - xhat * sum_gxhat / n),   dz = relu && z <= 0 ? 0 : dx
+// The ReLU and its backward mask ride in the loads; xhat is recomputed from z, never stored.
+//
+// BACKWARD IN DOUBLE: dx is what is left of g after its components along 1 and xhat are taken out,
+// plus a term of relative size eps * rstd^2.  Over few rows (n = 2: xhat = +-1 exactly spans the rest)
+// the projection cancels to that term, and every fp32 rounding on the way — of mean, of rstd, of the
+// two sums, of the products in the apply sweep — comes out multiplied by 1 / (eps * rstd^2): 3e-5 of
+// max|dz| at 2 x 16 standard normal rows, in torch's own fp32 evaluation as much as in an fp32 sweep
+// here.  So the backward pair does not pass fp32 through: bn_bwd_sums_kernel, which reads z anyway,
+// also carries sum t and sum t^2 of t = x - mean (exact in double, and centred, so nothing cancels),
+// and its finish kernel derives from them the mean's rounding error, var and rstd in double, and hands
+// the apply sweep four DOUBLE columns coef[4][F] = { mean, rstd, sum_g / n, rstd^2 * sum g (x - mean) / n };
+// bn_bwd_apply_kernel evaluates dx in double from them and rounds once, in the store.  That is
+// 5 FP64 instructions per element pair loaded, on a part whose FP64 vector rate is half its FP32 one:
+// the sweeps stay HBM-bound (DESIGN.md has the times).  sum_g / sum_gxhat (dbeta / dgamma) stay fp32 [F].
+//
+// Geometry of every sweep (that of bwd_colsum_kernel, gcn_spmm.hip): a 256-thread block owns a
+// contiguous slab of rows; thread t owns the 16 bytes (V = 4 fp32 / 8 bf16 columns) at column group
+// t % CG (CG = F / V) of every (256 / CG)-th row of the slab, so its per-column constants live in
+// registers for the whole slab.
+//
+// ACCUMULATION: the running sums (sum x, sum x^2; sum g, sum g * (x - mean)) are carried in DOUBLE,
+// per thread, per block and in the finish kernel.  A product of two fp32 numbers is exact in double,
+// so var = sum x^2 / n - mean^2 loses nothing to cancellation that fp32 could see (a column
+// 1000 + N(0,1) keeps its variance: the stored fp32 var is 6e-8 of float64, its own rounding; plain fp32
+// sums miss it by 9e-2).  Each block writes one
+// partial row [2][F]; bn_finish_kernel adds the partial rows in a fixed order — no float atomics,
+// bitwise reproducible.  The sweeps are HBM-bound: 3 FP64 instructions per element loaded.
+//
+// NaN / inf follow torch: relu keeps NaN (z < 0 ? 0 : z), an inf in a column gives mean = inf and
+// var = rstd = NaN for that column only, and the backward mask is torch's threshold_backward
+// (z <= 0 ? 0 : dx), so a NaN z lets its (NaN) dx through.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+
+#include "gcn_spmm.h"
+
+int gcn_internal_fail(int code, const char *msg);
+int gcn_internal_fail_hip(int hip_error, const char *where);
+
+namespace {
+
+typedef uint16_t bf16_t;
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+template <typename T> struct Lane;       // 16 bytes of a row <-> V floats
+template <> struct Lane<float> {
+    static constexpr int V = 4;
+    typedef f32x4 Raw;
+    static __device__ __forceinline__ void unpack(const Raw &r, float (&x)[4])
+    {
+        x[0] = r.x; x[1] = r.y; x[2] = r.z; x[3] = r.w;
+    }
+    static __device__ __forceinline__ Raw pack(const float (&x)[4])
+    {
+        Raw r = {x[0], x[1], x[2], x[3]};
+        return r;
+    }
+};
+template <> struct Lane<bf16_t> {
+    static constexpr int V = 8;
+    typedef u32x4 Raw;
+    static __device__ __forceinline__ void unpack(const Raw &r, float (&x)[8])
+    {
+        const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            x[2 * i] = __uint_as_float(w[i] << 16);
+            x[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+        }
+    }
+    static __device__ __forceinline__ uint32_t pair(float lo, float hi)
+    {
+        f32x2 v = {lo, hi};
+        bf16x2 b = __builtin_convertvector(v, bf16x2);   // v_cvt_pk_bf16_f32, round-to-nearest-even
+        return __builtin_bit_cast(uint32_t, b);
+    }
+    static __device__ __forceinline__ Raw pack(const float (&x)[8])
+    {
+        Raw r = {pair(x[0], x[1]), pair(x[2], x[3]), pair(x[4], x[5]), pair(x[6], x[7])};
+        return r;
+    }
+};
+
+// torch.relu: NaN stays NaN (fmaxf would drop it)
+__device__ __forceinline__ float act(float z, int relu) { return (relu && z < 0.f) ? 0.f : z; }
+
+// where a thread stands in its block's slab
+struct Place {
+    int CG, RL, cg, rl;
+    int64_t r0, r1;
+    __device__ __forceinline__ Place(int F, int V, int64_t n_rows, int rows_per_block)
+    {
+        CG = F / V; RL = 256 / CG;
+        cg = threadIdx.x % CG; rl = threadIdx.x / CG;
+        r0 = (int64_t)blockIdx.x * rows_per_block;
+        r1 = min(r0 + (int64_t)rows_per_block, n_rows);
+    }
+};
+
+// sums of the block's 256 / CG row lanes, added in lane order, written to dst[V * cg ..]
+template <int V>
+__device__ __forceinline__ void block_combine(double (&acc)[V], double *red, const Place &p, double *dst)
+{
+    __syncthreads();                      // (red may still be read from the previous call)
+#pragma unroll
+    for (int i = 0; i < V; ++i) red[threadIdx.x * V + i] = acc[i];
+    __syncthreads();
+    if (p.rl == 0) {
+        for (int k = 1; k < p.RL; ++k)    // fixed order
+#pragma unroll
+            for (int i = 0; i < V; ++i) acc[i] += red[(k * p.CG + p.cg) * V + i];
+#pragma unroll
+        for (int i = 0; i < V; ++i) dst[V * p.cg + i] = acc[i];
+    }
+}
+
+// partial[block][0][F] = sum x, partial[block][1][F] = sum x^2 over the block's slab
+template <typename T>
+__global__ __launch_bounds__(256) void bn_stats_kernel(const T *__restrict__ z, double *__restrict__ partial,
+                                                       int64_t n_rows, int F, int relu, int rows_per_block)
+{
+    constexpr int V = Lane<T>::V;
+    typedef typename Lane<T>::Raw Raw;
+    __shared__ double red[256 * V];
+    const Place p(F, V, n_rows, rows_per_block);
+    double s[V], q[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) s[i] = q[i] = 0.0;
+    for (int64_t r = p.r0 + p.rl; r < p.r1; r += p.RL) {
+        float x[V];
+        Lane<T>::unpack(*(const Raw *)(z + r * F + V * p.cg), x);
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const double d = (double)act(x[i], relu);
+            s[i] += d;
+            q[i] = fma(d, d, q[i]);
+        }
+    }
+    double *row = partial + (int64_t)blockIdx.x * 2 * F;
+    block_combine<V>(s, red, p, row);
+    block_combine<V>(q, red, p, row + F);
+}
+
+// partial[block][0..3][F] = sum g, sum g * t, sum t, sum t^2 over the block's slab, t = x - mean
+template <typename T>
+__global__ __launch_bounds__(256) void bn_bwd_sums_kernel(const T *__restrict__ g, const T *__restrict__ z,
+                                                          double *__restrict__ partial, int64_t n_rows, int F,
+                                                          int relu, int rows_per_block,
+                                                          const float *__restrict__ mean)
+{
+    constexpr int V = Lane<T>::V;
+    typedef typename Lane<T>::Raw Raw;
+    __shared__ double red[256 * V];
+    const Place p(F, V, n_rows, rows_per_block);
+    double mu[V], s[V], q[V], st[V], stt[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        mu[i] = (double)mean[V * p.cg + i];
+        s[i] = q[i] = st[i] = stt[i] = 0.0;
+    }
+    for (int64_t r = p.r0 + p.rl; r < p.r1; r += p.RL) {
+        const int64_t off = r * F + V * p.cg;
+        float x[V], gg[V];
+        Lane<T>::unpack(*(const Raw *)(g + off), gg);
+        Lane<T>::unpack(*(const Raw *)(z + off), x);
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const double d = (double)gg[i];
+            const double t = (double)act(x[i], relu) - mu[i];
+            s[i] += d;
+            q[i] = fma(d, t, q[i]);
+            st[i] += t;
+            stt[i] = fma(t, t, stt[i]);
+        }
+    }
+    double *row = partial + (int64_t)blockIdx.x * 4 * F;
+    block_combine<V>(s, red, p, row);
+    block_combine<V>(q, red, p, row + F);
+    block_combine<V>(st, red, p, row + 2 * F);
+    block_combine<V>(stt, red, p, row + 3 * F);
+}
+
+// y = (x - mean) * (rstd * gamma) + beta
+template <typename T>
+__global__ __launch_bounds__(256) void bn_apply_kernel(const T *__restrict__ z, T *__restrict__ y, int64_t n_rows,
+                                                       int F, int relu, int rows_per_block,
+                                                       const float *__restrict__ mean,
+                                                       const float *__restrict__ rstd,
+                                                       const float *__restrict__ gamma,
+                                                       const float *__restrict__ beta)
+{
+    constexpr int V = Lane<T>::V;
+    typedef typename Lane<T>::Raw Raw;
+    const Place p(F, V, n_rows, rows_per_block);
+    float mu[V], sc[V], sh[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const int f = V * p.cg + i;
+        mu[i] = mean[f];
+        sc[i] = gamma ? rstd[f] * gamma[f] : rstd[f];
+        sh[i] = beta ? beta[f] : 0.f;
+    }
+    for (int64_t r = p.r0 + p.rl; r < p.r1; r += p.RL) {
+        const int64_t off = r * F + V * p.cg;
+        float x[V];
+        Lane<T>::unpack(*(const Raw *)(z + off), x);
+#pragma unroll
+        for (int i = 0; i < V; ++i) x[i] = fmaf(act(x[i], relu) - mu[i], sc[i], sh[i]);
+        *(Raw *)(y + off) = Lane<T>::pack(x);
+    }
+}
+
+// dz = mask * gamma * rstd * (g - sum_g / n - (x - mean) * rstd^2 * sum g (x - mean) / n), in double from
+// coef[4][F] (see the file header); dz may alias g (a thread reads its 16 bytes of g before it writes
+// the same 16 bytes of dz)
+template <typename T>
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T *g, const T *__restrict__ z, T *dz,
+                                                           int64_t n_rows, int F, int relu, int rows_per_block,
+                                                           const float *__restrict__ gamma,
+                                                           const double *__restrict__ coef)
+{
+    constexpr int V = Lane<T>::V;
+    typedef typename Lane<T>::Raw Raw;
+    const Place p(F, V, n_rows, rows_per_block);
+    double mu[V], a[V], b[V], c[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const int f = V * p.cg + i;
+        mu[i] = coef[f];
+        a[i] = gamma ? coef[F + f] * (double)gamma[f] : coef[F + f];
+        b[i] = coef[2 * F + f];
+        c[i] = coef[3 * F + f];
+    }
+    for (int64_t r = p.r0 + p.rl; r < p.r1; r += p.RL) {
+        const int64_t off = r * F + V * p.cg;
+        float x[V], gg[V];
+        Lane<T>::unpack(*(const Raw *)(g + off), gg);
+        Lane<T>::unpack(*(const Raw *)(z + off), x);
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const double t = (double)act(x[i], relu) - mu[i];
+            const float dx = (float)(a[i] * fma(-t, c[i], (double)gg[i] - b[i]));
+            gg[i] = (relu && x[i] <= 0.f) ? 0.f : dx;     // torch's threshold_backward: NaN z passes dx
+        }
+        *(Raw *)(dz + off) = Lane<T>::pack(gg);
+    }
+}
+
+// partial[n_blocks][NS][F] -> per-column results.  A 1024-thread block owns 32 columns; thread (g, c)
+// adds the partial rows g, g+32, ... of column c, then the 32 group sums are added in group order
+// through LDS: a fixed order.
+//   NS = 2 (forward):  (sum x, sum x^2) -> mean, biased var, rstd                       fp32 [F]
+//   NS = 4 (backward): (sum g, sum g t, sum t, sum t^2), t = x - mean32 -> sum_g, sum_gxhat fp32 [F] and
+//                      coef[4][F] in double: the mean, var and rstd of the column to double precision
+//                      (mean = mean32 + sum t / n; var = sum t^2 / n - (sum t / n)^2, centred)
+template <int NS>
+__global__ __launch_bounds__(1024) void bn_finish_kernel(const double *__restrict__ partial, int n_blocks, int F,
+                                                         double n, float eps, const float *__restrict__ mean_in,
+                                                         float *__restrict__ out0, float *__restrict__ out1,
+                                                         float *__restrict__ out2, double *__restrict__ coef)
+{
+    __shared__ double red[NS][32][33];
+    const int c = threadIdx.x & 31, grp = threadIdx.x >> 5;
+    const int f = blockIdx.x * 32 + c;
+    double a[NS];
+#pragma unroll
+    for (int j = 0; j < NS; ++j) a[j] = 0.0;
+    if (f < F) {
+#pragma unroll 4
+        for (int k = grp; k < n_blocks; k += 32)
+#pragma unroll
+            for (int j = 0; j < NS; ++j) a[j] += partial[((int64_t)k * NS + j) * F + f];
+    }
+#pragma unroll
+    for (int j = 0; j < NS; ++j) red[j][grp][c] = a[j];
+    __syncthreads();
+    if (grp == 0 && f < F) {
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            a[j] = 0.0;
+            for (int k = 0; k < 32; ++k) a[j] += red[j][k][c];
+        }
+        if constexpr (NS == 2) {
+            const double m = a[0] / n;
+            double v = a[1] / n - m * m;
+            v = v < 0.0 ? 0.0 : v;                       // (keeps NaN)
+            out0[f] = (float)m;
+            out1[f] = (float)v;
+            out2[f] = (float)(1.0 / sqrt(v + (double)eps));
+        } else {
+            const double d = a[2] / n;                   // mean - mean32
+            double v = a[3] / n - d * d;
+            v = v < 0.0 ? 0.0 : v;
+            const double rs = 1.0 / sqrt(v + (double)eps);
+            const double sgx = a[1] - d * a[0];          // sum g (x - mean)
+            out0[f] = (float)a[0];
+            out1[f] = (float)(sgx * rs);
+            coef[f] = (double)mean_in[f] + d;
+            coef[F + f] = rs;
+            coef[2 * F + f] = a[0] / n;
+            coef[3 * F + f] = rs * rs * (sgx / n);
+        }
+    }
+}
+
+constexpr int64_t kBlocks = 2048;        // slabs of rows = partial rows (bwd_colsum_kernel's grid)
+
+struct Slabs {
+    int64_t blocks;
+    int rows_per_block;
+    explicit Slabs(int64_t n_rows)
+    {
+        blocks = std::min<int64_t>((n_rows + 63) / 64, kBlocks);
+        rows_per_block = (int)((n_rows + blocks - 1) / blocks);
+    }
+};
+
+bool shape_ok(int64_t n_rows, int64_t F, int dtype)
+{
+    if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16) return false;
+    const int64_t v = dtype == GCN_DTYPE_BF16 ? 8 : 4;   // elements per 16-byte lane
+    return n_rows >= 2 && n_rows <= (int64_t)INT32_MAX * kBlocks && F >= v && F <= 256 * v && (F % v) == 0 &&
+           (256 % (F / v)) == 0;
+}
+
+int bad(const char *who, int code, const char *what)
+{
+    char msg[200];
+    std::snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return gcn_internal_fail(code, msg);
+}
+
+// the argument checks every entry point shares; 0 = go on
+int check(const char *who, int dtype, int64_t n_rows, int64_t F, bool null_ptr, uintptr_t tensors)
+{
+    if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16) return bad(who, GCN_E_BADARG, "unknown dtype");
+    if (!shape_ok(n_rows, F, dtype))
+        return bad(who, GCN_E_BADARG,
+                   "needs n_rows >= 2 and F a multiple of the 16-byte lane width with F/width dividing 256");
+    if (null_ptr) return bad(who, GCN_E_BADARG, "NULL pointer");
+    if (tensors % 16 != 0) return bad(who, GCN_E_ALIGN, "16-byte alignment required");
+    return 0;
+}
+
+int launched(const char *who)
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, who);
+}
+
+}   // namespace
+
+extern "C" {
+
+size_t gcn_bn_workspace_bytes(int64_t n_rows, int64_t F, int dtype)
+{
+    if (!shape_ok(n_rows, F, dtype)) return 0;
+    return (size_t)Slabs(n_rows).blocks * 4 * (size_t)F * sizeof(double);    // backward: 4 sums per block
+}
+
+int gcn_bn_stats(int dtype, const void *z, int64_t n_rows, int64_t F, int relu, float eps, float *mean,
+                 float *var, float *rstd, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *who = "gcn_bn_stats";
+    if (int rc = check(who, dtype, n_rows, F, z == nullptr || mean == nullptr || var == nullptr || rstd == nullptr,
+                       (uintptr_t)z))
+        return rc;
+    if (workspace == nullptr || workspace_bytes < gcn_bn_workspace_bytes(n_rows, F, dtype))
+        return bad(who, GCN_E_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace % 16 != 0) return bad(who, GCN_E_ALIGN, "16-byte alignment required");
+    const Slabs sl(n_rows);
+    const dim3 grid((unsigned)sl.blocks), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    double *part = (double *)workspace;
+    if (dtype == GCN_DTYPE_F32)
+        hipLaunchKernelGGL(bn_stats_kernel<float>, grid, block, 0, s, (const float *)z, part, n_rows, (int)F, relu,
+                           sl.rows_per_block);
+    else
+        hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)z, part, n_rows, (int)F, relu,
+                           sl.rows_per_block);
+    hipLaunchKernelGGL(bn_finish_kernel<2>, dim3((unsigned)((F + 31) / 32)), dim3(1024), 0, s,
+                       (const double *)part, (int)sl.blocks, (int)F, (double)n_rows, eps, (const float *)nullptr,
+                       mean, var, rstd, (double *)nullptr);
+    return launched(who);
+}
+
+int gcn_bn_apply(int dtype, const void *z, void *y, int64_t n_rows, int64_t F, int relu, const float *mean,
+                 const float *rstd, const float *gamma, const float *beta, void *stream)
+{
+    const char *who = "gcn_bn_apply";
+    if (int rc = check(who, dtype, n_rows, F, z == nullptr || y == nullptr || mean == nullptr || rstd == nullptr,
+                       (uintptr_t)z | (uintptr_t)y))
+        return rc;
+    const Slabs sl(n_rows);
+    const dim3 grid((unsigned)sl.blocks), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == GCN_DTYPE_F32)
+        hipLaunchKernelGGL(bn_apply_kernel<float>, grid, block, 0, s, (const float *)z, (float *)y, n_rows, (int)F,
+                           relu, sl.rows_per_block, mean, rstd, gamma, beta);
+    else
+        hipLaunchKernelGGL(bn_apply_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)z, (bf16_t *)y, n_rows,
+                           (int)F, relu, sl.rows_per_block, mean, rstd, gamma, beta);
+    return launched(who);
+}
+
+int gcn_bn_backward_sums(int dtype, const void *g, const void *z, int64_t n_rows, int64_t F, int relu, float eps,
+                         const float *mean, float *sum_g, float *sum_gxhat, double *coef, void *workspace,
+                         size_t workspace_bytes, void *stream)
+{
+    const char *who = "gcn_bn_backward_sums";
+    if (int rc = check(who, dtype, n_rows, F,
+                       g == nullptr || z == nullptr || mean == nullptr || sum_g == nullptr ||
+                           sum_gxhat == nullptr || coef == nullptr,
+                       (uintptr_t)g | (uintptr_t)z))
+        return rc;
+    if (workspace == nullptr || workspace_bytes < gcn_bn_workspace_bytes(n_rows, F, dtype))
+        return bad(who, GCN_E_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace % 16 != 0 || (uintptr_t)coef % 8 != 0)
+        return bad(who, GCN_E_ALIGN, "16-byte alignment required (coef: 8)");
+    const Slabs sl(n_rows);
+    const dim3 grid((unsigned)sl.blocks), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    double *part = (double *)workspace;
+    if (dtype == GCN_DTYPE_F32)
+        hipLaunchKernelGGL(bn_bwd_sums_kernel<float>, grid, block, 0, s, (const float *)g, (const float *)z, part,
+                           n_rows, (int)F, relu, sl.rows_per_block, mean);
+    else
+        hipLaunchKernelGGL(bn_bwd_sums_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)g, (const bf16_t *)z, part,
+                           n_rows, (int)F, relu, sl.rows_per_block, mean);
+    hipLaunchKernelGGL(bn_finish_kernel<4>, dim3((unsigned)((F + 31) / 32)), dim3(1024), 0, s,
+                       (const double *)part, (int)sl.blocks, (int)F, (double)n_rows, eps, mean, sum_g, sum_gxhat,
+                       (float *)nullptr, coef);
+    return launched(who);
+}
+
+int gcn_bn_backward_apply(int dtype, const void *g, const void *z, void *dz, int64_t n_rows, int64_t F, int relu,
+                          const float *gamma, const double *coef, void *stream)
+{
+    const char *who = "gcn_bn_backward_apply";
+    if (int rc = check(who, dtype, n_rows, F, g == nullptr || z == nullptr || dz == nullptr || coef == nullptr,
+                       (uintptr_t)g | (uintptr_t)z | (uintptr_t)dz))
+        return rc;
+    if ((uintptr_t)coef % 8 != 0) return bad(who, GCN_E_ALIGN, "coef: 8-byte alignment required");
+    const Slabs sl(n_rows);
+    const dim3 grid((unsigned)sl.blocks), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == GCN_DTYPE_F32)
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, grid, block, 0, s, (const float *)g, (const float *)z,
+                           (float *)dz, n_rows, (int)F, relu, sl.rows_per_block, gamma, coef);
+    else
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)g, (const bf16_t *)z,
+                           (bf16_t *)dz, n_rows, (int)F, relu, sl.rows_per_block, gamma, coef);
+    return launched(who);
+}
+
+}   // extern "C"

@@ -5,8 +5,16 @@ torch's `nll_loss` kernels walk one row per thread: on the [|idx_train|, 256] sl
 (517 k rows) forward + backward take 2.0 ms per epoch; a gather of one element per row and a
 scatter of one element per row into a zero tensor take 0.3 ms.  Same value, same gradient.
 """
+import os
+import sys
+
 import torch
 import torch.utils._pytree as pytree
+
+if not __package__:   # flat import, the reference's convention (`from functional import nll_loss`)
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+# the fork's apply_bn(F.relu(.)) (pygcn/models.py:49,53) as HIP sweeps: pygcn_amd/norm.py
+from pygcn_amd.norm import relu_batch_norm  # noqa: E402,F401
 
 
 class NLLGrad(torch.Tensor):

@@ -14,6 +14,8 @@ if not __package__:   # flat import, the reference's convention (`from models im
     from layers import GraphConvolution
 else:
     from pygcn_amd.layers import GraphConvolution
+from pygcn_amd.norm import relu_batch_norm  # noqa: E402
+from pygcn_amd.sharded import ShardedGraph  # noqa: E402
 from pygcn_amd.tuning import ROWGRAD_MIN_ROWS  # noqa: E402
 
 
@@ -111,3 +113,35 @@ class GCNStack(nn.Module):
         for i in range(self.nlayers):
             x = getattr(self, f"gc{i + 1}")(x, adj, relu=True)
         return x
+
+
+class GCNBatchNorm(nn.Module):
+    """The model the reference fork runs today (reference pygcn/models.py:17-71, its `GCN`): three
+    GraphConvolutions, ReLU + BatchNorm after the first two, ReLU after the third, the result
+    returned as is (:71):
+
+        x = apply_bn(F.relu(gc1(x, adj)))      :49   apply_bn = nn.BatchNorm1d(x.size(1)).cuda()(x), :41-45
+        x = apply_bn(F.relu(gc2(x, adj)))      :53
+        x = F.relu(gc3(x, adj))                :56
+
+    Parameters gc1..gc3 with weight / bias: the fork's state_dict keys, and nothing else — the fork
+    builds a FRESH BatchNorm1d on every call, so the normalisation has no learned or running state
+    (gamma = 1, beta = 0) and uses batch statistics under `model.eval()` too; so does this class.
+    `dropout` and `NN` are stored and unused, as in the fork.  ReLU + BatchNorm run as the HIP
+    sweeps of pygcn_amd/norm.py, the last ReLU in the store of gc3's sparse product."""
+
+    def __init__(self, nfeat, nhid, nclass, dropout, NN=None):
+        super(GCNBatchNorm, self).__init__()
+        self.gc1 = GraphConvolution(nfeat, nhid)
+        self.gc2 = GraphConvolution(nhid, nhid)
+        self.gc3 = GraphConvolution(nhid, nclass)
+        self.dropout = dropout
+        self.NN = NN
+
+    def forward(self, x, adj):
+        if isinstance(adj, ShardedGraph):
+            raise RuntimeError("GCNBatchNorm: a ShardedGraph adjacency is not supported — BatchNorm's "
+                               "statistics run over all vertices, and cross-rank statistics are not built")
+        x = relu_batch_norm(self.gc1(x, adj))
+        x = relu_batch_norm(self.gc2(x, adj))
+        return self.gc3(x, adj, relu=True)
