@@ -74,6 +74,13 @@ typedef struct gcn_csr_plan {
 
 /* ABI history: 21 = round 2's surface.  26: the ReLU + BatchNorm sweeps gcn_bn_workspace_bytes / gcn_bn_stats /
  * gcn_bn_apply / gcn_bn_backward_sums / gcn_bn_backward_apply — new entry points only; nothing existing changed.
+ * Additive to 26 (the number did not move: a library without them fails to bind with a message naming the
+ * missing symbol): the column-window forms gcn_bn_batched_workspace_bytes / gcn_bn_stats_batched /
+ * gcn_bn_apply_batched / gcn_bn_backward_sums_batched / gcn_bn_backward_apply_batched for k samples side by
+ * side (the fork's per-sample loop, reference pygcn/models.py:343-349) and the masked mean pool
+ * gcn_pool_workspace_bytes / gcn_masked_colsum / gcn_masked_broadcast (its PoolLayer, reference
+ * pygcn/models.py:267-286); the existing gcn_bn_ entry points are now the batch = 1 launch of the same kernels,
+ * with the same results.
  * 25 (round 4, late): new entry point gcn_gemm_atg256_f32_b3_colsum (the
  * weight gradient with the bias gradient Σ G[rows] as a side result); gcn_gemm_atg256_workspace_bytes grew by
  * 1 KiB per workgroup; struct gcn_gemm_epilogue gained keep_bits_out / mask_bits at its END (zero them);
@@ -587,6 +594,57 @@ int gcn_bn_backward_sums(int dtype, const void *g, const void *z, int64_t n_rows
                          size_t workspace_bytes, void *stream);
 int gcn_bn_backward_apply(int dtype, const void *g, const void *z, void *dz, int64_t n_rows, int64_t F, int relu,
                           const float *gamma, const double *coef, void *stream);
+
+/*
+ * The same four sweeps over `batch` COLUMN WINDOWS of a contiguous row-major [n_rows, batch * F] matrix:
+ * window j is the columns [j * F, (j + 1) * F), read with the row pitch batch * F.  This is the layout in
+ * which GraphConvolution holds k samples over one graph side by side, so that per-sample BatchNorm — the
+ * fork runs its model once per sample in a Python loop, "cannot batch yet", reference
+ * pygcn/models.py:343-349 — is per-column BatchNorm of ONE matrix, in one launch per sweep.
+ * F obeys the shape rule above (the WINDOW width; batch * F is free), 1 <= batch <= 65535 (else
+ * GCN_E_BADARG).  The per-column vectors mean, var, rstd, sum_g, sum_gxhat, gamma, beta have batch * F
+ * entries (window after window; gamma, beta may be NULL), coef is [4][batch * F] double.
+ * A window's results are BITWISE those of the 2-D entry point on a contiguous [n_rows, F] copy of the
+ * window, whatever `batch` is: same slabs, same lanes, same summation orders (the 2-D entry points are
+ * the batch = 1 launch of the same kernels).  Errors, alignment, NaN / inf and aliasing as above.
+ *     gcn_bn_batched_workspace_bytes = batch * gcn_bn_workspace_bytes(n_rows, F, dtype)
+ * (window j's partial rows at byte j * gcn_bn_workspace_bytes); 0 outside the rule.
+ * (ABI 26, additive.)
+ */
+size_t gcn_bn_batched_workspace_bytes(int64_t n_rows, int64_t F, int64_t batch, int dtype);
+int gcn_bn_stats_batched(int dtype, const void *z, int64_t n_rows, int64_t F, int64_t batch, int relu, float eps,
+                         float *mean, float *var, float *rstd, void *workspace, size_t workspace_bytes,
+                         void *stream);
+int gcn_bn_apply_batched(int dtype, const void *z, void *y, int64_t n_rows, int64_t F, int64_t batch, int relu,
+                         const float *mean, const float *rstd, const float *gamma, const float *beta, void *stream);
+int gcn_bn_backward_sums_batched(int dtype, const void *g, const void *z, int64_t n_rows, int64_t F, int64_t batch,
+                                 int relu, float eps, const float *mean, float *sum_g, float *sum_gxhat,
+                                 double *coef, void *workspace, size_t workspace_bytes, void *stream);
+int gcn_bn_backward_apply_batched(int dtype, const void *g, const void *z, void *dz, int64_t n_rows, int64_t F,
+                                  int64_t batch, int relu, const float *gamma, const double *coef, void *stream);
+
+/*
+ * Masked column sums over the same layout — the reduction of the fork's PoolLayer (reference
+ * pygcn/models.py:267-286: every sample's [N, C] output is multiplied by a 0/1 vertex mask, summed over
+ * the vertices and divided by a vertex count).  h is a contiguous [n_rows, batch * C] matrix (fp32 / bf16),
+ * mask a contiguous fp32 [batch, n_rows] (sample after sample, as the fork holds it):
+ *     gcn_masked_colsum      sums[j * C + c] = sum_r mask[j, r] * h[r, j * C + c]        one read sweep
+ *     gcn_masked_broadcast   dh[r, j * C + c] = mask[j, r] * coef[j * C + c]             one write sweep
+ * `sums` is DEVICE double [batch * C] (8-byte aligned): products and sums are carried in double per
+ * thread, per block and in the finish kernel, added in a fixed order — no float atomics, bitwise
+ * reproducible; the division by the count is the caller's.  The mask MULTIPLIES (0 * NaN = NaN, as in
+ * the fork).  `coef` is DEVICE fp32 [batch * C]; the product is fp32, rounded once in the store of dh.
+ * C obeys the shape rule above, n_rows >= 1, 1 <= batch <= 65535 (else GCN_E_BADARG); h, dh and the
+ * workspace 16-byte aligned (GCN_E_ALIGN).
+ *     gcn_pool_workspace_bytes = batch * B * C * sizeof(double),  B = min(ceil(n_rows / 64), 2048);
+ * 0 outside the rule.
+ * (ABI 26, additive.)
+ */
+size_t gcn_pool_workspace_bytes(int64_t n_rows, int64_t C, int64_t batch, int dtype);
+int gcn_masked_colsum(int dtype, const void *h, const float *mask, int64_t n_rows, int64_t C, int64_t batch,
+                      double *sums, void *workspace, size_t workspace_bytes, void *stream);
+int gcn_masked_broadcast(int dtype, const float *mask, const float *coef, void *dh, int64_t n_rows, int64_t C,
+                         int64_t batch, void *stream);
 
 #ifdef __cplusplus
 }

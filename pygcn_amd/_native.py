@@ -113,6 +113,14 @@ SIGNATURES = {
     "gcn_bn_apply": (i, [i, p, p, i64, i64, i, p, p, p, p, p]),
     "gcn_bn_backward_sums": (i, [i, p, p, i64, i64, i, f32, p, p, p, p, p, sz, p]),
     "gcn_bn_backward_apply": (i, [i, p, p, p, i64, i64, i, p, p, p]),
+    "gcn_bn_batched_workspace_bytes": (sz, [i64, i64, i64, i]),
+    "gcn_bn_stats_batched": (i, [i, p, i64, i64, i64, i, f32, p, p, p, p, sz, p]),
+    "gcn_bn_apply_batched": (i, [i, p, p, i64, i64, i64, i, p, p, p, p, p]),
+    "gcn_bn_backward_sums_batched": (i, [i, p, p, i64, i64, i64, i, f32, p, p, p, p, p, sz, p]),
+    "gcn_bn_backward_apply_batched": (i, [i, p, p, p, i64, i64, i64, i, p, p, p]),
+    "gcn_pool_workspace_bytes": (sz, [i64, i64, i64, i]),
+    "gcn_masked_colsum": (i, [i, p, p, i64, i64, i64, p, p, sz, p]),
+    "gcn_masked_broadcast": (i, [i, p, p, p, i64, i64, i64, p]),
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -135,8 +143,15 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:   # e.g. libamdhip64 not found
         raise NativeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
+    bound = []
     for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(L, name)
+        try:
+            fn = getattr(L, name)
+        except AttributeError:      # (entry points were added without moving the ABI number)
+            raise NativeLibraryError(f"{LIB_PATH} does not export {name}: a library older than this package; "
+                                     "rebuild with `python -m pygcn_amd.build`") from None
+        bound.append((fn, restype, argtypes))
+    for fn, restype, argtypes in bound:
         fn.restype, fn.argtypes = restype, argtypes
     if L.gcn_abi_version() != GCN_ABI_VERSION:
         raise NativeLibraryError(f"{LIB_PATH}: ABI version {L.gcn_abi_version()} != "

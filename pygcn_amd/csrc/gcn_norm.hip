@@ -38,6 +38,21 @@
 // partial row [2][F]; bn_finish_kernel adds the partial rows in a fixed order — no float atomics,
 // bitwise reproducible.  The sweeps are HBM-bound: 3 FP64 instructions per element loaded.
 //
+// COLUMN WINDOWS (the *_batched entry points): k samples over the same vertices lie side by side as
+// [n_rows, k * F] (GraphConvolution's batched layout), and per-sample BatchNorm is per-column BatchNorm of
+// that matrix.  gridDim.y walks the k windows [j * F, (j + 1) * F): a block sweeps its slab of ONE window
+// with the row pitch k * F, so the window width obeys the shape rule and k is free.  The slabs, the lane
+// of every thread, the partial layout of a window and every summation order are those of the 2-D sweep
+// (which is the k = 1 launch of the same kernels): a window's results are, bit for bit, what the 2-D
+// entry point returns on a contiguous copy of the window.
+//
+// MASKED MEAN POOL (the fork's PoolLayer, reference pygcn/models.py:267-286) over the same layout:
+// pool_colsum_kernel is bn_stats_kernel with a per-row, per-window weight mask[j, r] and one sum;
+// pool_broadcast_kernel writes its gradient mask[j, r] * coef[j * C + c] in one sweep.  The mask stays
+// [k, n_rows], as the caller holds it: a block's slab reads consecutive floats of ONE mask row.  (As
+// [n_rows, k] every row of a window fetched 4 bytes of a line of its own: measured at 10^6 x (20 x 32)
+// fp32, 4.6 instead of 5.8 TB/s for the sum and 3.8 instead of 4.8 for the broadcast.)
+//
 // NaN / inf follow torch: relu keeps NaN (z < 0 ? 0 : z), an inf in a column gives mean = inf and
 // var = rstd = NaN for that column only, and the backward mask is torch's threshold_backward
 // (z <= 0 ? 0 : dx), so a NaN z lets its (NaN) dx through.
@@ -102,17 +117,24 @@ template <> struct Lane<bf16_t> {
 // torch.relu: NaN stays NaN (fmaxf would drop it)
 __device__ __forceinline__ float act(float z, int relu) { return (relu && z < 0.f) ? 0.f : z; }
 
-// where a thread stands in its block's slab
+// where a thread stands in its block's slab, and the slab in the matrix: blockIdx.y is the column
+// window [w0, w0 + F) of a [n_rows, gridDim.y * F] matrix (one window, pitch F: the 2-D entry points)
 struct Place {
     int CG, RL, cg, rl;
-    int64_t r0, r1;
+    int64_t r0, r1, ld;
+    int c0;                               // the thread's first column in the whole matrix
     __device__ __forceinline__ Place(int F, int V, int64_t n_rows, int rows_per_block)
     {
         CG = F / V; RL = 256 / CG;
         cg = threadIdx.x % CG; rl = threadIdx.x / CG;
         r0 = (int64_t)blockIdx.x * rows_per_block;
         r1 = min(r0 + (int64_t)rows_per_block, n_rows);
+        ld = (int64_t)gridDim.y * F;
+        c0 = (int)blockIdx.y * F + V * cg;
     }
+    __device__ __forceinline__ int64_t at(int64_t r) const { return r * ld + c0; }
+    // the block's partial row: window after window, each laid out as the 2-D sweep's [gridDim.x][NS][F]
+    __device__ __forceinline__ int64_t slot() const { return (int64_t)blockIdx.y * gridDim.x + blockIdx.x; }
 };
 
 // sums of the block's 256 / CG row lanes, added in lane order, written to dst[V * cg ..]
@@ -146,7 +168,7 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const T *__restrict__ z, 
     for (int i = 0; i < V; ++i) s[i] = q[i] = 0.0;
     for (int64_t r = p.r0 + p.rl; r < p.r1; r += p.RL) {
         float x[V];
-        Lane<T>::unpack(*(const Raw *)(z + r * F + V * p.cg), x);
+        Lane<T>::unpack(*(const Raw *)(z + p.at(r)), x);
 #pragma unroll
         for (int i = 0; i < V; ++i) {
             const double d = (double)act(x[i], relu);
@@ -154,7 +176,7 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const T *__restrict__ z, 
             q[i] = fma(d, d, q[i]);
         }
     }
-    double *row = partial + (int64_t)blockIdx.x * 2 * F;
+    double *row = partial + p.slot() * 2 * F;
     block_combine<V>(s, red, p, row);
     block_combine<V>(q, red, p, row + F);
 }
@@ -173,11 +195,11 @@ __global__ __launch_bounds__(256) void bn_bwd_sums_kernel(const T *__restrict__ 
     double mu[V], s[V], q[V], st[V], stt[V];
 #pragma unroll
     for (int i = 0; i < V; ++i) {
-        mu[i] = (double)mean[V * p.cg + i];
+        mu[i] = (double)mean[p.c0 + i];
         s[i] = q[i] = st[i] = stt[i] = 0.0;
     }
     for (int64_t r = p.r0 + p.rl; r < p.r1; r += p.RL) {
-        const int64_t off = r * F + V * p.cg;
+        const int64_t off = p.at(r);
         float x[V], gg[V];
         Lane<T>::unpack(*(const Raw *)(g + off), gg);
         Lane<T>::unpack(*(const Raw *)(z + off), x);
@@ -191,7 +213,7 @@ __global__ __launch_bounds__(256) void bn_bwd_sums_kernel(const T *__restrict__ 
             stt[i] = fma(t, t, stt[i]);
         }
     }
-    double *row = partial + (int64_t)blockIdx.x * 4 * F;
+    double *row = partial + p.slot() * 4 * F;
     block_combine<V>(s, red, p, row);
     block_combine<V>(q, red, p, row + F);
     block_combine<V>(st, red, p, row + 2 * F);
@@ -213,13 +235,13 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T *__restrict__ z, 
     float mu[V], sc[V], sh[V];
 #pragma unroll
     for (int i = 0; i < V; ++i) {
-        const int f = V * p.cg + i;
+        const int f = p.c0 + i;
         mu[i] = mean[f];
         sc[i] = gamma ? rstd[f] * gamma[f] : rstd[f];
         sh[i] = beta ? beta[f] : 0.f;
     }
     for (int64_t r = p.r0 + p.rl; r < p.r1; r += p.RL) {
-        const int64_t off = r * F + V * p.cg;
+        const int64_t off = p.at(r);
         float x[V];
         Lane<T>::unpack(*(const Raw *)(z + off), x);
 #pragma unroll
@@ -229,7 +251,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T *__restrict__ z, 
 }
 
 // dz = mask * gamma * rstd * (g - sum_g / n - (x - mean) * rstd^2 * sum g (x - mean) / n), in double from
-// coef[4][F] (see the file header); dz may alias g (a thread reads its 16 bytes of g before it writes
+// coef[4][ld] (see the file header); dz may alias g (a thread reads its 16 bytes of g before it writes
 // the same 16 bytes of dz)
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T *g, const T *__restrict__ z, T *dz,
@@ -243,14 +265,14 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T *g, const T *
     double mu[V], a[V], b[V], c[V];
 #pragma unroll
     for (int i = 0; i < V; ++i) {
-        const int f = V * p.cg + i;
+        const int f = p.c0 + i;
         mu[i] = coef[f];
-        a[i] = gamma ? coef[F + f] * (double)gamma[f] : coef[F + f];
-        b[i] = coef[2 * F + f];
-        c[i] = coef[3 * F + f];
+        a[i] = gamma ? coef[p.ld + f] * (double)gamma[f] : coef[p.ld + f];
+        b[i] = coef[2 * p.ld + f];
+        c[i] = coef[3 * p.ld + f];
     }
     for (int64_t r = p.r0 + p.rl; r < p.r1; r += p.RL) {
-        const int64_t off = r * F + V * p.cg;
+        const int64_t off = p.at(r);
         float x[V], gg[V];
         Lane<T>::unpack(*(const Raw *)(g + off), gg);
         Lane<T>::unpack(*(const Raw *)(z + off), x);
@@ -264,13 +286,15 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T *g, const T *
     }
 }
 
-// partial[n_blocks][NS][F] -> per-column results.  A 1024-thread block owns 32 columns; thread (g, c)
-// adds the partial rows g, g+32, ... of column c, then the 32 group sums are added in group order
-// through LDS: a fixed order.
-//   NS = 2 (forward):  (sum x, sum x^2) -> mean, biased var, rstd                       fp32 [F]
-//   NS = 4 (backward): (sum g, sum g t, sum t, sum t^2), t = x - mean32 -> sum_g, sum_gxhat fp32 [F] and
-//                      coef[4][F] in double: the mean, var and rstd of the column to double precision
-//                      (mean = mean32 + sum t / n; var = sum t^2 / n - (sum t / n)^2, centred)
+// partial[window][n_blocks][NS][F] -> per-column results of window blockIdx.y, written at columns
+// [window * F, (window + 1) * F) of vectors of length gridDim.y * F.  A 1024-thread block owns 32 columns;
+// thread (g, c) adds the partial rows g, g+32, ... of column c, then the 32 group sums are added in group
+// order through LDS: a fixed order, the same for a window as for the 2-D sweep (gridDim.y = 1).
+//   NS = 2 (forward):  (sum x, sum x^2) -> mean, biased var, rstd                       fp32
+//   NS = 4 (backward): (sum g, sum g t, sum t, sum t^2), t = x - mean32 -> sum_g, sum_gxhat fp32 and
+//                      coef[4][gridDim.y * F] in double: the mean, var and rstd of the column to double
+//                      precision (mean = mean32 + sum t / n; var = sum t^2 / n - (sum t / n)^2, centred)
+//   NS = 1 (pool):     the sum itself, in double -> coef
 template <int NS>
 __global__ __launch_bounds__(1024) void bn_finish_kernel(const double *__restrict__ partial, int n_blocks, int F,
                                                          double n, float eps, const float *__restrict__ mean_in,
@@ -280,6 +304,9 @@ __global__ __launch_bounds__(1024) void bn_finish_kernel(const double *__restric
     __shared__ double red[NS][32][33];
     const int c = threadIdx.x & 31, grp = threadIdx.x >> 5;
     const int f = blockIdx.x * 32 + c;
+    const int64_t ld = (int64_t)gridDim.y * F;
+    const int64_t o = (int64_t)blockIdx.y * F + f;       // the column in the whole matrix
+    partial += (int64_t)blockIdx.y * n_blocks * NS * F;
     double a[NS];
 #pragma unroll
     for (int j = 0; j < NS; ++j) a[j] = 0.0;
@@ -298,30 +325,78 @@ __global__ __launch_bounds__(1024) void bn_finish_kernel(const double *__restric
             a[j] = 0.0;
             for (int k = 0; k < 32; ++k) a[j] += red[j][k][c];
         }
-        if constexpr (NS == 2) {
+        if constexpr (NS == 1) {
+            coef[o] = a[0];
+        } else if constexpr (NS == 2) {
             const double m = a[0] / n;
             double v = a[1] / n - m * m;
             v = v < 0.0 ? 0.0 : v;                       // (keeps NaN)
-            out0[f] = (float)m;
-            out1[f] = (float)v;
-            out2[f] = (float)(1.0 / sqrt(v + (double)eps));
+            out0[o] = (float)m;
+            out1[o] = (float)v;
+            out2[o] = (float)(1.0 / sqrt(v + (double)eps));
         } else {
             const double d = a[2] / n;                   // mean - mean32
             double v = a[3] / n - d * d;
             v = v < 0.0 ? 0.0 : v;
             const double rs = 1.0 / sqrt(v + (double)eps);
             const double sgx = a[1] - d * a[0];          // sum g (x - mean)
-            out0[f] = (float)a[0];
-            out1[f] = (float)(sgx * rs);
-            coef[f] = (double)mean_in[f] + d;
-            coef[F + f] = rs;
-            coef[2 * F + f] = a[0] / n;
-            coef[3 * F + f] = rs * rs * (sgx / n);
+            out0[o] = (float)a[0];
+            out1[o] = (float)(sgx * rs);
+            coef[o] = (double)mean_in[o] + d;
+            coef[ld + o] = rs;
+            coef[2 * ld + o] = a[0] / n;
+            coef[3 * ld + o] = rs * rs * (sgx / n);
         }
     }
 }
 
+// masked column sums of window blockIdx.y: partial[slot][F] = sum_r mask[window, r] * h[r, window's columns]
+// over the block's slab (a product of two fp32 numbers is exact in double)
+template <typename T>
+__global__ __launch_bounds__(256) void pool_colsum_kernel(const T *__restrict__ h, const float *__restrict__ mask,
+                                                          double *__restrict__ partial, int64_t n_rows, int F,
+                                                          int rows_per_block)
+{
+    constexpr int V = Lane<T>::V;
+    typedef typename Lane<T>::Raw Raw;
+    __shared__ double red[256 * V];
+    const Place p(F, V, n_rows, rows_per_block);
+    double s[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) s[i] = 0.0;
+    for (int64_t r = p.r0 + p.rl; r < p.r1; r += p.RL) {
+        const double m = (double)mask[(int64_t)blockIdx.y * n_rows + r];
+        float x[V];
+        Lane<T>::unpack(*(const Raw *)(h + p.at(r)), x);
+#pragma unroll
+        for (int i = 0; i < V; ++i) s[i] = fma(m, (double)x[i], s[i]);   // 0 * NaN = NaN, as torch's product
+    }
+    block_combine<V>(s, red, p, partial + p.slot() * F);
+}
+
+// dh[r, window's columns] = mask[window, r] * coef[window's columns]
+template <typename T>
+__global__ __launch_bounds__(256) void pool_broadcast_kernel(const float *__restrict__ mask,
+                                                             const float *__restrict__ coef, T *__restrict__ dh,
+                                                             int64_t n_rows, int F, int rows_per_block)
+{
+    constexpr int V = Lane<T>::V;
+    typedef typename Lane<T>::Raw Raw;
+    const Place p(F, V, n_rows, rows_per_block);
+    float c[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) c[i] = coef[p.c0 + i];
+    for (int64_t r = p.r0 + p.rl; r < p.r1; r += p.RL) {
+        const float m = mask[(int64_t)blockIdx.y * n_rows + r];
+        float x[V];
+#pragma unroll
+        for (int i = 0; i < V; ++i) x[i] = m * c[i];
+        *(Raw *)(dh + p.at(r)) = Lane<T>::pack(x);
+    }
+}
+
 constexpr int64_t kBlocks = 2048;        // slabs of rows = partial rows (bwd_colsum_kernel's grid)
+constexpr int64_t kMaxBatch = 65535;     // windows ride on gridDim.y
 
 struct Slabs {
     int64_t blocks;
@@ -333,13 +408,19 @@ struct Slabs {
     }
 };
 
-bool shape_ok(int64_t n_rows, int64_t F, int dtype)
+bool width_ok(int64_t F, int dtype)
 {
     if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16) return false;
     const int64_t v = dtype == GCN_DTYPE_BF16 ? 8 : 4;   // elements per 16-byte lane
-    return n_rows >= 2 && n_rows <= (int64_t)INT32_MAX * kBlocks && F >= v && F <= 256 * v && (F % v) == 0 &&
-           (256 % (F / v)) == 0;
+    return F >= v && F <= 256 * v && (F % v) == 0 && (256 % (F / v)) == 0;
 }
+
+bool shape_ok(int64_t n_rows, int64_t F, int dtype)
+{
+    return n_rows >= 2 && n_rows <= (int64_t)INT32_MAX * kBlocks && width_ok(F, dtype);
+}
+
+bool batch_ok(int64_t batch) { return batch >= 1 && batch <= kMaxBatch; }
 
 int bad(const char *who, int code, const char *what)
 {
@@ -348,13 +429,28 @@ int bad(const char *who, int code, const char *what)
     return gcn_internal_fail(code, msg);
 }
 
-// the argument checks every entry point shares; 0 = go on
-int check(const char *who, int dtype, int64_t n_rows, int64_t F, bool null_ptr, uintptr_t tensors)
+// the argument checks every BatchNorm entry point shares; 0 = go on
+int check(const char *who, int dtype, int64_t n_rows, int64_t F, int64_t batch, bool null_ptr, uintptr_t tensors)
 {
     if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16) return bad(who, GCN_E_BADARG, "unknown dtype");
     if (!shape_ok(n_rows, F, dtype))
         return bad(who, GCN_E_BADARG,
                    "needs n_rows >= 2 and F a multiple of the 16-byte lane width with F/width dividing 256");
+    if (!batch_ok(batch)) return bad(who, GCN_E_BADARG, "needs 1 <= batch <= 65535");
+    if (null_ptr) return bad(who, GCN_E_BADARG, "NULL pointer");
+    if (tensors % 16 != 0) return bad(who, GCN_E_ALIGN, "16-byte alignment required");
+    return 0;
+}
+
+// the same for the two pool sweeps, which take a single row
+int check_pool(const char *who, int dtype, int64_t n_rows, int64_t C, int64_t batch, bool null_ptr,
+               uintptr_t tensors)
+{
+    if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16) return bad(who, GCN_E_BADARG, "unknown dtype");
+    if (n_rows < 1 || n_rows > (int64_t)INT32_MAX * kBlocks || !width_ok(C, dtype))
+        return bad(who, GCN_E_BADARG,
+                   "needs n_rows >= 1 and C a multiple of the 16-byte lane width with C/width dividing 256");
+    if (!batch_ok(batch)) return bad(who, GCN_E_BADARG, "needs 1 <= batch <= 65535");
     if (null_ptr) return bad(who, GCN_E_BADARG, "NULL pointer");
     if (tensors % 16 != 0) return bad(who, GCN_E_ALIGN, "16-byte alignment required");
     return 0;
@@ -364,6 +460,101 @@ int launched(const char *who)
 {
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, who);
+}
+
+dim3 finish_grid(int64_t F, int64_t batch) { return dim3((unsigned)((F + 31) / 32), (unsigned)batch); }
+
+// The four sweeps over `batch` column windows of width F; the 2-D entry points are batch = 1.
+int stats(const char *who, int dtype, const void *z, int64_t n_rows, int64_t F, int64_t batch, int relu, float eps,
+          float *mean, float *var, float *rstd, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (int rc = check(who, dtype, n_rows, F, batch,
+                       z == nullptr || mean == nullptr || var == nullptr || rstd == nullptr, (uintptr_t)z))
+        return rc;
+    if (workspace == nullptr || workspace_bytes < gcn_bn_batched_workspace_bytes(n_rows, F, batch, dtype))
+        return bad(who, GCN_E_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace % 16 != 0) return bad(who, GCN_E_ALIGN, "16-byte alignment required");
+    const Slabs sl(n_rows);
+    const dim3 grid((unsigned)sl.blocks, (unsigned)batch), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    double *part = (double *)workspace;
+    if (dtype == GCN_DTYPE_F32)
+        hipLaunchKernelGGL(bn_stats_kernel<float>, grid, block, 0, s, (const float *)z, part, n_rows, (int)F, relu,
+                           sl.rows_per_block);
+    else
+        hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)z, part, n_rows, (int)F, relu,
+                           sl.rows_per_block);
+    hipLaunchKernelGGL(bn_finish_kernel<2>, finish_grid(F, batch), dim3(1024), 0, s, (const double *)part,
+                       (int)sl.blocks, (int)F, (double)n_rows, eps, (const float *)nullptr, mean, var, rstd,
+                       (double *)nullptr);
+    return launched(who);
+}
+
+int apply(const char *who, int dtype, const void *z, void *y, int64_t n_rows, int64_t F, int64_t batch, int relu,
+          const float *mean, const float *rstd, const float *gamma, const float *beta, void *stream)
+{
+    if (int rc = check(who, dtype, n_rows, F, batch,
+                       z == nullptr || y == nullptr || mean == nullptr || rstd == nullptr,
+                       (uintptr_t)z | (uintptr_t)y))
+        return rc;
+    const Slabs sl(n_rows);
+    const dim3 grid((unsigned)sl.blocks, (unsigned)batch), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == GCN_DTYPE_F32)
+        hipLaunchKernelGGL(bn_apply_kernel<float>, grid, block, 0, s, (const float *)z, (float *)y, n_rows, (int)F,
+                           relu, sl.rows_per_block, mean, rstd, gamma, beta);
+    else
+        hipLaunchKernelGGL(bn_apply_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)z, (bf16_t *)y, n_rows,
+                           (int)F, relu, sl.rows_per_block, mean, rstd, gamma, beta);
+    return launched(who);
+}
+
+int backward_sums(const char *who, int dtype, const void *g, const void *z, int64_t n_rows, int64_t F,
+                  int64_t batch, int relu, float eps, const float *mean, float *sum_g, float *sum_gxhat,
+                  double *coef, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (int rc = check(who, dtype, n_rows, F, batch,
+                       g == nullptr || z == nullptr || mean == nullptr || sum_g == nullptr ||
+                           sum_gxhat == nullptr || coef == nullptr,
+                       (uintptr_t)g | (uintptr_t)z))
+        return rc;
+    if (workspace == nullptr || workspace_bytes < gcn_bn_batched_workspace_bytes(n_rows, F, batch, dtype))
+        return bad(who, GCN_E_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace % 16 != 0 || (uintptr_t)coef % 8 != 0)
+        return bad(who, GCN_E_ALIGN, "16-byte alignment required (coef: 8)");
+    const Slabs sl(n_rows);
+    const dim3 grid((unsigned)sl.blocks, (unsigned)batch), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    double *part = (double *)workspace;
+    if (dtype == GCN_DTYPE_F32)
+        hipLaunchKernelGGL(bn_bwd_sums_kernel<float>, grid, block, 0, s, (const float *)g, (const float *)z, part,
+                           n_rows, (int)F, relu, sl.rows_per_block, mean);
+    else
+        hipLaunchKernelGGL(bn_bwd_sums_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)g, (const bf16_t *)z, part,
+                           n_rows, (int)F, relu, sl.rows_per_block, mean);
+    hipLaunchKernelGGL(bn_finish_kernel<4>, finish_grid(F, batch), dim3(1024), 0, s, (const double *)part,
+                       (int)sl.blocks, (int)F, (double)n_rows, eps, mean, sum_g, sum_gxhat, (float *)nullptr, coef);
+    return launched(who);
+}
+
+int backward_apply(const char *who, int dtype, const void *g, const void *z, void *dz, int64_t n_rows, int64_t F,
+                   int64_t batch, int relu, const float *gamma, const double *coef, void *stream)
+{
+    if (int rc = check(who, dtype, n_rows, F, batch,
+                       g == nullptr || z == nullptr || dz == nullptr || coef == nullptr,
+                       (uintptr_t)g | (uintptr_t)z | (uintptr_t)dz))
+        return rc;
+    if ((uintptr_t)coef % 8 != 0) return bad(who, GCN_E_ALIGN, "coef: 8-byte alignment required");
+    const Slabs sl(n_rows);
+    const dim3 grid((unsigned)sl.blocks, (unsigned)batch), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == GCN_DTYPE_F32)
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, grid, block, 0, s, (const float *)g, (const float *)z,
+                           (float *)dz, n_rows, (int)F, relu, sl.rows_per_block, gamma, coef);
+    else
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)g, (const bf16_t *)z,
+                           (bf16_t *)dz, n_rows, (int)F, relu, sl.rows_per_block, gamma, coef);
+    return launched(who);
 }
 
 }   // namespace
@@ -376,98 +567,118 @@ size_t gcn_bn_workspace_bytes(int64_t n_rows, int64_t F, int dtype)
     return (size_t)Slabs(n_rows).blocks * 4 * (size_t)F * sizeof(double);    // backward: 4 sums per block
 }
 
+size_t gcn_bn_batched_workspace_bytes(int64_t n_rows, int64_t F, int64_t batch, int dtype)
+{
+    return batch_ok(batch) ? (size_t)batch * gcn_bn_workspace_bytes(n_rows, F, dtype) : 0;
+}
+
 int gcn_bn_stats(int dtype, const void *z, int64_t n_rows, int64_t F, int relu, float eps, float *mean,
                  float *var, float *rstd, void *workspace, size_t workspace_bytes, void *stream)
 {
-    const char *who = "gcn_bn_stats";
-    if (int rc = check(who, dtype, n_rows, F, z == nullptr || mean == nullptr || var == nullptr || rstd == nullptr,
-                       (uintptr_t)z))
-        return rc;
-    if (workspace == nullptr || workspace_bytes < gcn_bn_workspace_bytes(n_rows, F, dtype))
-        return bad(who, GCN_E_WORKSPACE, "workspace too small");
-    if ((uintptr_t)workspace % 16 != 0) return bad(who, GCN_E_ALIGN, "16-byte alignment required");
-    const Slabs sl(n_rows);
-    const dim3 grid((unsigned)sl.blocks), block(256);
-    hipStream_t s = (hipStream_t)stream;
-    double *part = (double *)workspace;
-    if (dtype == GCN_DTYPE_F32)
-        hipLaunchKernelGGL(bn_stats_kernel<float>, grid, block, 0, s, (const float *)z, part, n_rows, (int)F, relu,
-                           sl.rows_per_block);
-    else
-        hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)z, part, n_rows, (int)F, relu,
-                           sl.rows_per_block);
-    hipLaunchKernelGGL(bn_finish_kernel<2>, dim3((unsigned)((F + 31) / 32)), dim3(1024), 0, s,
-                       (const double *)part, (int)sl.blocks, (int)F, (double)n_rows, eps, (const float *)nullptr,
-                       mean, var, rstd, (double *)nullptr);
-    return launched(who);
+    return stats("gcn_bn_stats", dtype, z, n_rows, F, 1, relu, eps, mean, var, rstd, workspace, workspace_bytes,
+                 stream);
 }
 
 int gcn_bn_apply(int dtype, const void *z, void *y, int64_t n_rows, int64_t F, int relu, const float *mean,
                  const float *rstd, const float *gamma, const float *beta, void *stream)
 {
-    const char *who = "gcn_bn_apply";
-    if (int rc = check(who, dtype, n_rows, F, z == nullptr || y == nullptr || mean == nullptr || rstd == nullptr,
-                       (uintptr_t)z | (uintptr_t)y))
-        return rc;
-    const Slabs sl(n_rows);
-    const dim3 grid((unsigned)sl.blocks), block(256);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == GCN_DTYPE_F32)
-        hipLaunchKernelGGL(bn_apply_kernel<float>, grid, block, 0, s, (const float *)z, (float *)y, n_rows, (int)F,
-                           relu, sl.rows_per_block, mean, rstd, gamma, beta);
-    else
-        hipLaunchKernelGGL(bn_apply_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)z, (bf16_t *)y, n_rows,
-                           (int)F, relu, sl.rows_per_block, mean, rstd, gamma, beta);
-    return launched(who);
+    return apply("gcn_bn_apply", dtype, z, y, n_rows, F, 1, relu, mean, rstd, gamma, beta, stream);
 }
 
 int gcn_bn_backward_sums(int dtype, const void *g, const void *z, int64_t n_rows, int64_t F, int relu, float eps,
                          const float *mean, float *sum_g, float *sum_gxhat, double *coef, void *workspace,
                          size_t workspace_bytes, void *stream)
 {
-    const char *who = "gcn_bn_backward_sums";
-    if (int rc = check(who, dtype, n_rows, F,
-                       g == nullptr || z == nullptr || mean == nullptr || sum_g == nullptr ||
-                           sum_gxhat == nullptr || coef == nullptr,
-                       (uintptr_t)g | (uintptr_t)z))
-        return rc;
-    if (workspace == nullptr || workspace_bytes < gcn_bn_workspace_bytes(n_rows, F, dtype))
-        return bad(who, GCN_E_WORKSPACE, "workspace too small");
-    if ((uintptr_t)workspace % 16 != 0 || (uintptr_t)coef % 8 != 0)
-        return bad(who, GCN_E_ALIGN, "16-byte alignment required (coef: 8)");
-    const Slabs sl(n_rows);
-    const dim3 grid((unsigned)sl.blocks), block(256);
-    hipStream_t s = (hipStream_t)stream;
-    double *part = (double *)workspace;
-    if (dtype == GCN_DTYPE_F32)
-        hipLaunchKernelGGL(bn_bwd_sums_kernel<float>, grid, block, 0, s, (const float *)g, (const float *)z, part,
-                           n_rows, (int)F, relu, sl.rows_per_block, mean);
-    else
-        hipLaunchKernelGGL(bn_bwd_sums_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)g, (const bf16_t *)z, part,
-                           n_rows, (int)F, relu, sl.rows_per_block, mean);
-    hipLaunchKernelGGL(bn_finish_kernel<4>, dim3((unsigned)((F + 31) / 32)), dim3(1024), 0, s,
-                       (const double *)part, (int)sl.blocks, (int)F, (double)n_rows, eps, mean, sum_g, sum_gxhat,
-                       (float *)nullptr, coef);
-    return launched(who);
+    return backward_sums("gcn_bn_backward_sums", dtype, g, z, n_rows, F, 1, relu, eps, mean, sum_g, sum_gxhat, coef,
+                         workspace, workspace_bytes, stream);
 }
 
 int gcn_bn_backward_apply(int dtype, const void *g, const void *z, void *dz, int64_t n_rows, int64_t F, int relu,
                           const float *gamma, const double *coef, void *stream)
 {
-    const char *who = "gcn_bn_backward_apply";
-    if (int rc = check(who, dtype, n_rows, F, g == nullptr || z == nullptr || dz == nullptr || coef == nullptr,
-                       (uintptr_t)g | (uintptr_t)z | (uintptr_t)dz))
+    return backward_apply("gcn_bn_backward_apply", dtype, g, z, dz, n_rows, F, 1, relu, gamma, coef, stream);
+}
+
+int gcn_bn_stats_batched(int dtype, const void *z, int64_t n_rows, int64_t F, int64_t batch, int relu, float eps,
+                         float *mean, float *var, float *rstd, void *workspace, size_t workspace_bytes,
+                         void *stream)
+{
+    return stats("gcn_bn_stats_batched", dtype, z, n_rows, F, batch, relu, eps, mean, var, rstd, workspace,
+                 workspace_bytes, stream);
+}
+
+int gcn_bn_apply_batched(int dtype, const void *z, void *y, int64_t n_rows, int64_t F, int64_t batch, int relu,
+                         const float *mean, const float *rstd, const float *gamma, const float *beta, void *stream)
+{
+    return apply("gcn_bn_apply_batched", dtype, z, y, n_rows, F, batch, relu, mean, rstd, gamma, beta, stream);
+}
+
+int gcn_bn_backward_sums_batched(int dtype, const void *g, const void *z, int64_t n_rows, int64_t F, int64_t batch,
+                                 int relu, float eps, const float *mean, float *sum_g, float *sum_gxhat,
+                                 double *coef, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return backward_sums("gcn_bn_backward_sums_batched", dtype, g, z, n_rows, F, batch, relu, eps, mean, sum_g,
+                         sum_gxhat, coef, workspace, workspace_bytes, stream);
+}
+
+int gcn_bn_backward_apply_batched(int dtype, const void *g, const void *z, void *dz, int64_t n_rows, int64_t F,
+                                  int64_t batch, int relu, const float *gamma, const double *coef, void *stream)
+{
+    return backward_apply("gcn_bn_backward_apply_batched", dtype, g, z, dz, n_rows, F, batch, relu, gamma, coef,
+                          stream);
+}
+
+size_t gcn_pool_workspace_bytes(int64_t n_rows, int64_t C, int64_t batch, int dtype)
+{
+    if (n_rows < 1 || n_rows > (int64_t)INT32_MAX * kBlocks || !width_ok(C, dtype) || !batch_ok(batch)) return 0;
+    return (size_t)batch * (size_t)Slabs(n_rows).blocks * (size_t)C * sizeof(double);   // one sum per block
+}
+
+int gcn_masked_colsum(int dtype, const void *h, const float *mask, int64_t n_rows, int64_t C, int64_t batch,
+                      double *sums, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *who = "gcn_masked_colsum";
+    if (int rc = check_pool(who, dtype, n_rows, C, batch, h == nullptr || mask == nullptr || sums == nullptr,
+                            (uintptr_t)h))
         return rc;
-    if ((uintptr_t)coef % 8 != 0) return bad(who, GCN_E_ALIGN, "coef: 8-byte alignment required");
+    if (workspace == nullptr || workspace_bytes < gcn_pool_workspace_bytes(n_rows, C, batch, dtype))
+        return bad(who, GCN_E_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace % 16 != 0 || (uintptr_t)sums % 8 != 0 || (uintptr_t)mask % 4 != 0)
+        return bad(who, GCN_E_ALIGN, "16-byte alignment required (sums: 8, mask: 4)");
     const Slabs sl(n_rows);
-    const dim3 grid((unsigned)sl.blocks), block(256);
+    const dim3 grid((unsigned)sl.blocks, (unsigned)batch), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    double *part = (double *)workspace;
+    if (dtype == GCN_DTYPE_F32)
+        hipLaunchKernelGGL(pool_colsum_kernel<float>, grid, block, 0, s, (const float *)h, mask, part, n_rows,
+                           (int)C, sl.rows_per_block);
+    else
+        hipLaunchKernelGGL(pool_colsum_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)h, mask, part, n_rows,
+                           (int)C, sl.rows_per_block);
+    hipLaunchKernelGGL(bn_finish_kernel<1>, finish_grid(C, batch), dim3(1024), 0, s, (const double *)part,
+                       (int)sl.blocks, (int)C, 1.0, 0.f, (const float *)nullptr, (float *)nullptr, (float *)nullptr,
+                       (float *)nullptr, sums);
+    return launched(who);
+}
+
+int gcn_masked_broadcast(int dtype, const float *mask, const float *coef, void *dh, int64_t n_rows, int64_t C,
+                         int64_t batch, void *stream)
+{
+    const char *who = "gcn_masked_broadcast";
+    if (int rc = check_pool(who, dtype, n_rows, C, batch, mask == nullptr || coef == nullptr || dh == nullptr,
+                            (uintptr_t)dh))
+        return rc;
+    if ((uintptr_t)mask % 4 != 0 || (uintptr_t)coef % 4 != 0)
+        return bad(who, GCN_E_ALIGN, "mask, coef: 4-byte alignment required");
+    const Slabs sl(n_rows);
+    const dim3 grid((unsigned)sl.blocks, (unsigned)batch), block(256);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == GCN_DTYPE_F32)
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, grid, block, 0, s, (const float *)g, (const float *)z,
-                           (float *)dz, n_rows, (int)F, relu, sl.rows_per_block, gamma, coef);
+        hipLaunchKernelGGL(pool_broadcast_kernel<float>, grid, block, 0, s, mask, coef, (float *)dh, n_rows, (int)C,
+                           sl.rows_per_block);
     else
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)g, (const bf16_t *)z,
-                           (bf16_t *)dz, n_rows, (int)F, relu, sl.rows_per_block, gamma, coef);
+        hipLaunchKernelGGL(pool_broadcast_kernel<bf16_t>, grid, block, 0, s, mask, coef, (bf16_t *)dh, n_rows,
+                           (int)C, sl.rows_per_block);
     return launched(who);
 }
 

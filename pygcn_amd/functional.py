@@ -15,6 +15,8 @@ if not __package__:   # flat import, the reference's convention (`from functiona
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 # the fork's apply_bn(F.relu(.)) (pygcn/models.py:49,53) as HIP sweeps: pygcn_amd/norm.py
 from pygcn_amd.norm import relu_batch_norm  # noqa: E402,F401
+# the readout of its evaluator, PoolLayer (pygcn/models.py:267-286), for all samples at once: pygcn_amd/pool.py
+from pygcn_amd.pool import masked_mean_pool  # noqa: E402,F401
 
 
 class NLLGrad(torch.Tensor):

@@ -123,17 +123,30 @@ class GraphConvolution(Module):
         k, n, _ = input.shape
         support = torch.matmul(input, self.weight)                       # [k, N, Fout]
         wide = support.permute(1, 0, 2).reshape(n, k * self.out_features)
+        out = self._aggregate_wide(wide, adj, k, relu)
+        return out.view(n, k, self.out_features).permute(1, 0, 2)
+
+    def _aggregate_wide(self, wide, adj, k, relu):
+        """adj · wide + bias (ReLU) for k supports side by side, wide [N, k·Fout]: one sparse product
+        on k·Fout-wide rows, the bias repeated k times."""
         bias = self.bias.repeat(k) if self.bias is not None else None
         if isinstance(adj, torch.Tensor) and adj.layout == torch.strided:
             out = torch.mm(adj, wide)
             out = out + bias if bias is not None else out
-            out = torch.relu(out) if relu else out
-        elif isinstance(adj, ShardedGraph):
-            out = ShardedSpMMFunction.apply(adj, wide.contiguous(), bias, relu)
-        else:
-            _require_cuda(input, "input")
-            out = SpMMFunction.apply(as_graph(adj), wide, bias, relu)
-        return out.view(n, k, self.out_features).permute(1, 0, 2)
+            return torch.relu(out) if relu else out
+        if isinstance(adj, ShardedGraph):
+            return ShardedSpMMFunction.apply(adj, wide.contiguous(), bias, relu)
+        _require_cuda(wide, "input")
+        return SpMMFunction.apply(as_graph(adj), wide, bias, relu)
+
+    def forward_wide(self, wide, adj, k, relu=False):
+        """The layer on k samples that STAY side by side: wide [N, k·Fin] -> [N, k·Fout], both
+        contiguous with sample j in the columns [j·F, (j+1)·F) — the layout _forward_batched aggregates
+        in, kept from layer to layer so that a stack of layers transposes nothing (GCNBatchNorm).
+        X·W is one GEMM on the free view [N·k, Fin] (the hand-written kernels at 256 -> 256, M = N·k)."""
+        n = wide.shape[0]
+        support = DenseMMFunction.apply(wide.reshape(n * k, self.in_features), self.weight)
+        return self._aggregate_wide(support.view(n, k * self.out_features), adj, k, relu)
 
     def __repr__(self):
         return self.__class__.__name__ + ' (' \

@@ -128,7 +128,11 @@ class GCNBatchNorm(nn.Module):
     builds a FRESH BatchNorm1d on every call, so the normalisation has no learned or running state
     (gamma = 1, beta = 0) and uses batch statistics under `model.eval()` too; so does this class.
     `dropout` and `NN` are stored and unused, as in the fork.  ReLU + BatchNorm run as the HIP
-    sweeps of pygcn_amd/norm.py, the last ReLU in the store of gc3's sparse product."""
+    sweeps of pygcn_amd/norm.py, the last ReLU in the store of gc3's sparse product.
+
+    A 3-D input [k, N, nfeat] is k samples over the same graph (the fork's evaluator GCN_OVER_MLP
+    loops over them, :343-349): the result is [k, N, nclass], each sample normalised on its own, all
+    k in one pass (_forward_batched)."""
 
     def __init__(self, nfeat, nhid, nclass, dropout, NN=None):
         super(GCNBatchNorm, self).__init__()
@@ -142,6 +146,23 @@ class GCNBatchNorm(nn.Module):
         if isinstance(adj, ShardedGraph):
             raise RuntimeError("GCNBatchNorm: a ShardedGraph adjacency is not supported — BatchNorm's "
                                "statistics run over all vertices, and cross-rank statistics are not built")
+        if x.dim() == 3:
+            return self._forward_batched(x, adj)
         x = relu_batch_norm(self.gc1(x, adj))
         x = relu_batch_norm(self.gc2(x, adj))
         return self.gc3(x, adj, relu=True)
+
+    def _forward_batched(self, x, adj):
+        """x [k, N, nfeat] -> [k, N, nclass], equal to `torch.stack([self(x[j], adj) for j in range(k)])`
+        — the loop the fork's evaluator runs ("cannot batch yet", reference pygcn/models.py:343-349) —
+        in one pass: ONE permute of the input to [N, k, nfeat], then every layer works on k samples
+        side by side, [N, k·F] (GraphConvolution.forward_wide), where per-sample BatchNorm is
+        per-column BatchNorm (`relu_batch_norm(batch=k)`) and the next X·W a GEMM on the free view
+        [N·k, F]: no transpose between the layers.  The result is the permuted view of the
+        [N, k·nclass] storage — the layout `functional.masked_mean_pool` reads in place."""
+        k, n, nfeat = x.shape
+        h = x.permute(1, 0, 2).reshape(n, k * nfeat)
+        h = relu_batch_norm(self.gc1.forward_wide(h, adj, k), batch=k)
+        h = relu_batch_norm(self.gc2.forward_wide(h, adj, k), batch=k)
+        out = self.gc3.forward_wide(h, adj, k, relu=True)
+        return out.view(n, k, self.gc3.out_features).permute(1, 0, 2)
