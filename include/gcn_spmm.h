@@ -80,7 +80,9 @@ typedef struct gcn_csr_plan {
  * side (the fork's per-sample loop, reference pygcn/models.py:343-349) and the masked mean pool
  * gcn_pool_workspace_bytes / gcn_masked_colsum / gcn_masked_broadcast (its PoolLayer, reference
  * pygcn/models.py:267-286); the existing gcn_bn_ entry points are now the batch = 1 launch of the same kernels,
- * with the same results.
+ * with the same results.  Also additive to 26: the vertex-attention sweeps gcn_attn_workspace_bytes /
+ * gcn_attn_scores / gcn_attn_normalize / gcn_attn_backward (the head of its SoftGenerator, reference
+ * pygcn/models.py:324-329).
  * 25 (round 4, late): new entry point gcn_gemm_atg256_f32_b3_colsum (the
  * weight gradient with the bias gradient Σ G[rows] as a side result); gcn_gemm_atg256_workspace_bytes grew by
  * 1 KiB per workgroup; struct gcn_gemm_epilogue gained keep_bits_out / mask_bits at its END (zero them);
@@ -645,6 +647,44 @@ int gcn_masked_colsum(int dtype, const void *h, const float *mask, int64_t n_row
                       double *sums, void *workspace, size_t workspace_bytes, void *stream);
 int gcn_masked_broadcast(int dtype, const float *mask, const float *coef, void *dh, int64_t n_rows, int64_t C,
                          int64_t batch, void *stream);
+
+/*
+ * Vertex attention over the same layout — the head of the fork's SoftGenerator (reference
+ * pygcn/models.py:324-329: attn = softmax over the vertices of torch.mul(key, x).sum(dim=1)).  h is a
+ * contiguous [n_rows, batch * C] matrix (fp32 / bf16), key DEVICE fp32 [batch * C]; every per-row vector
+ * (scores, attn, ds) is fp32 [batch, n_rows], one window's rows consecutive, as the pool's mask.  Per window j:
+ *     s_r = sum_c key[j, c] * h[r, j * C + c]      M = max_r s_r      Z = sum_r exp(s_r - M)
+ *     attn_r = exp(s_r - M) / Z
+ *     backward, ds_r = attn_r * (g_r - sum_r g_r attn_r) formed by the caller ([batch, n_rows] work):
+ *     dh[r, j * C + c] = ds_r * key[j, c]          dkey[j, c] = sum_r ds_r * h[r, j * C + c]
+ *   gcn_attn_scores     one read sweep of h: the dot is carried in double, rounded ONCE and stored as
+ *                       scores[j, r]; the same launch reduces (M, Z) in double over each block's slab FROM
+ *                       THE ROUNDED SCORE (every later pass sees the same number), one pair per block and
+ *                       window, and a finish launch merges the pairs in a fixed order into
+ *                       `stats`, DEVICE double [batch, 2] = (M_j, Z_j), 8-byte aligned.
+ *   gcn_attn_normalize  attn[j, r] = (float)(exp((double)scores[j, r] - M_j) / Z_j): a pass over
+ *                       [batch, n_rows] floats; attn may alias scores.
+ *   gcn_attn_backward   one sweep: reads h and ds, writes dh (fp32 product, rounded once in the store) and
+ *                       accumulates dkey in double exactly as gcn_masked_colsum accumulates its sums; a finish
+ *                       launch writes `dkey`, DEVICE double [batch * C], 8-byte aligned.  dh may be NULL: the
+ *                       store is skipped and the call is one read of h.
+ * No float atomics, every sum in a fixed order: bitwise reproducible, and window j of a batched call is,
+ * bit for bit, the batch = 1 call on a contiguous copy of the window.  A NaN in a window's h makes that
+ * window's attn all NaN (torch's softmax) and leaves the other windows' bits alone.
+ * C obeys the shape rule above, n_rows >= 1, 1 <= batch <= 65535 (else GCN_E_BADARG); h, dh and the
+ * workspace 16-byte aligned (GCN_E_ALIGN).  Scratch of gcn_attn_scores and gcn_attn_backward:
+ *     gcn_attn_workspace_bytes = batch * B * max(C, 2) * sizeof(double),  B = min(ceil(n_rows / 64), 2048);
+ * 0 outside the rule.
+ * (ABI 26, additive.)
+ */
+size_t gcn_attn_workspace_bytes(int64_t n_rows, int64_t C, int64_t batch, int dtype);
+int gcn_attn_scores(int dtype, const void *h, const float *key, int64_t n_rows, int64_t C, int64_t batch,
+                    float *scores, double *stats, void *workspace, size_t workspace_bytes, void *stream);
+int gcn_attn_normalize(const float *scores, const double *stats, float *attn, int64_t n_rows, int64_t batch,
+                       void *stream);
+int gcn_attn_backward(int dtype, const void *h, const float *ds, const float *key, void *dh, double *dkey,
+                      int64_t n_rows, int64_t C, int64_t batch, void *workspace, size_t workspace_bytes,
+                      void *stream);
 
 #ifdef __cplusplus
 }

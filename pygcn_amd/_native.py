@@ -121,6 +121,10 @@ SIGNATURES = {
     "gcn_pool_workspace_bytes": (sz, [i64, i64, i64, i]),
     "gcn_masked_colsum": (i, [i, p, p, i64, i64, i64, p, p, sz, p]),
     "gcn_masked_broadcast": (i, [i, p, p, p, i64, i64, i64, p]),
+    "gcn_attn_workspace_bytes": (sz, [i64, i64, i64, i]),
+    "gcn_attn_scores": (i, [i, p, p, i64, i64, i64, p, p, p, sz, p]),
+    "gcn_attn_normalize": (i, [p, p, p, i64, i64, p]),
+    "gcn_attn_backward": (i, [i, p, p, p, p, p, i64, i64, i64, p, sz, p]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -53,6 +53,20 @@
 // [n_rows, k] every row of a window fetched 4 bytes of a line of its own: measured at 10^6 x (20 x 32)
 // fp32, 4.6 instead of 5.8 TB/s for the sum and 3.8 instead of 4.8 for the broadcast.)
 //
+// VERTEX ATTENTION (the head of the fork's SoftGenerator, reference pygcn/models.py:324-329:
+// attn = softmax over the vertices of torch.mul(key, x).sum(dim=1)) over the same layout, one key [C] per
+// window, every per-row vector [k, n_rows] as the pool's mask:
+//     forward   attn_scores_kernel    reads h      -> s[j, r] = key_j . h[r, window j], rounded once to fp32,
+//                                                     and per block (max, sum exp(s - max)) of the ROUNDED scores
+//               attn_finish_kernel    merges the per-block pairs in a fixed order -> (M, Z) per window, double
+//               attn_normalize_kernel [k, n_rows] floats: attn = exp(s - M) / Z
+//     backward  attn_backward_kernel  reads h, ds  -> writes dh = ds[r] * key, sums dkey = sum_r ds[r] * h[r, :]
+//                                                     as pool_colsum_kernel does (then bn_finish_kernel<1>)
+// ds = attn * (g - sum g attn) is [k, n_rows]-sized work left to the caller.  The dot of a row is carried in
+// double by the CG threads of the row and added by cross-lane moves (and through LDS where a row spans 2 or
+// 4 waves); the exponentials are double, evaluated once per row with all lanes busy.  A NaN score makes the
+// window's Z, and with it every attn of the window, NaN — torch's softmax — and touches no other window.
+//
 // NaN / inf follow torch: relu keeps NaN (z < 0 ? 0 : z), an inf in a column gives mean = inf and
 // var = rstd = NaN for that column only, and the backward mask is torch's threshold_backward
 // (z <= 0 ? 0 : dx), so a NaN z lets its (NaN) dx through.
@@ -395,6 +409,172 @@ __global__ __launch_bounds__(256) void pool_broadcast_kernel(const float *__rest
     }
 }
 
+// ---- vertex attention: attn = softmax over the rows of (h . key), per window (file header)
+//
+// a running (max, sum of exp(s - max)) of a set of scores, in double.  z == 0 marks the empty set (a
+// non-empty one has z >= 1 or NaN), so an empty slab or lane drops out instead of giving exp(-inf + inf)
+struct MaxSum {
+    double m, z;
+    __device__ __forceinline__ void add(float s)
+    {
+        const double d = (double)s;
+        const double e = exp(-fabs(d - m));              // NaN s: e = NaN, the comparison fails, z = NaN
+        if (d > m) { z = fma(z, e, 1.0); m = d; }
+        else z += e;
+    }
+    __device__ __forceinline__ void merge(double m2, double z2)
+    {
+        if (z2 == 0.0) return;
+        if (z == 0.0) { m = m2; z = z2; return; }
+        const double top = m2 > m ? m2 : m;
+        z = z * exp(m - top) + z2 * exp(m2 - top);
+        m = top;
+    }
+};
+
+// the 256 MaxSums of a block merged as a fixed tree through LDS; the result is thread 0's
+__device__ __forceinline__ void block_merge(MaxSum &a, double *red_m, double *red_z)
+{
+    red_m[threadIdx.x] = a.m;
+    red_z[threadIdx.x] = a.z;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            a.merge(red_m[threadIdx.x + s], red_z[threadIdx.x + s]);
+            red_m[threadIdx.x] = a.m;
+            red_z[threadIdx.x] = a.z;
+        }
+        __syncthreads();
+    }
+}
+
+// scores[window, r] = (float) sum_c key[window's columns] * h[r, window's columns], and the block's
+// MaxSum of its slab's ROUNDED scores -> partial[slot][2].
+// The CG threads of a row are consecutive lanes.  Their partial dots (double) are added by a butterfly
+// of cross-lane moves over min(CG, 64) lanes — a + b = b + a, so every lane of the row holds the same
+// bits — and for CG = 128 / 256 the 2 / 4 wave sums of the row are added in wave order through LDS.
+// The row's lane (iteration % min(CG, 64)) of its first wave rounds, stores and keeps the score; every
+// min(CG, 64) iterations all lanes fold the score they keep into their MaxSum at once, so the double
+// exp costs one evaluation per 64 rows and not one per row.  Every trip count is block-uniform.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_scores_kernel(const T *__restrict__ h, const float *__restrict__ key,
+                                                          float *__restrict__ scores, double *__restrict__ partial,
+                                                          int64_t n_rows, int C, int rows_per_block)
+{
+    constexpr int V = Lane<T>::V;
+    typedef typename Lane<T>::Raw Raw;
+    __shared__ double wsum[2][4];
+    __shared__ double red_m[256], red_z[256];
+    const Place p(C, V, n_rows, rows_per_block);
+    const int W = p.CG < 64 ? p.CG : 64;                 // lanes of a row within one wave
+    const int wave = threadIdx.x >> 6;
+    double kk[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) kk[i] = (double)key[p.c0 + i];
+    MaxSum acc = {-INFINITY, 0.0};
+    float kept = 0.f;
+    bool keeps = false;
+    int it = 0;
+    for (int64_t base = p.r0; base < p.r1; base += p.RL, ++it) {
+        const int64_t r = base + p.rl;
+        const bool live = r < p.r1;
+        double d = 0.0;
+        if (live) {
+            float x[V];
+            Lane<T>::unpack(*(const Raw *)(h + p.at(r)), x);
+#pragma unroll
+            for (int i = 0; i < V; ++i) d = fma(kk[i], (double)x[i], d);
+        }
+        for (int m = 1; m < W; m <<= 1) d += __shfl_xor(d, m, 64);
+        if (p.CG > 64) {                                 // (block-uniform)
+            if ((threadIdx.x & 63) == 0) wsum[it & 1][wave] = d;
+            __syncthreads();                             // (the other buffer is the previous iteration's)
+            const int w0 = p.rl * (p.CG >> 6);
+            d = wsum[it & 1][w0];
+            for (int w = 1; w < (p.CG >> 6); ++w) d += wsum[it & 1][w0 + w];
+        }
+        const int turn = it & (W - 1);
+        if (live && p.cg == turn) {                      // (cg < W: the row's first wave)
+            kept = (float)d;
+            keeps = true;
+            scores[(int64_t)blockIdx.y * n_rows + r] = kept;
+        }
+        if (turn == W - 1) {
+            if (keeps) acc.add(kept);
+            keeps = false;
+        }
+    }
+    if (keeps) acc.add(kept);
+    block_merge(acc, red_m, red_z);
+    if (threadIdx.x == 0) {
+        partial[p.slot() * 2] = acc.m;
+        partial[p.slot() * 2 + 1] = acc.z;
+    }
+}
+
+// stats[window] = (M, Z) of the window's n_blocks partial pairs: thread t merges the pairs t, t + 256, ...
+// in that order, then the 256 threads merge as block_merge's tree — a fixed order, the same for every batch
+__global__ __launch_bounds__(256) void attn_finish_kernel(const double *__restrict__ partial, int n_blocks,
+                                                          double *__restrict__ stats)
+{
+    __shared__ double red_m[256], red_z[256];
+    partial += (int64_t)blockIdx.x * n_blocks * 2;
+    MaxSum acc = {-INFINITY, 0.0};
+    for (int b = threadIdx.x; b < n_blocks; b += 256) acc.merge(partial[2 * b], partial[2 * b + 1]);
+    block_merge(acc, red_m, red_z);
+    if (threadIdx.x == 0) {
+        stats[2 * blockIdx.x] = acc.m;
+        stats[2 * blockIdx.x + 1] = acc.z;
+    }
+}
+
+// attn[window, r] = (float)(exp(s - M) / Z); attn may alias scores (a thread reads its float before it
+// writes the same float)
+__global__ __launch_bounds__(256) void attn_normalize_kernel(const float *scores, const double *__restrict__ stats,
+                                                             float *attn, int64_t n_rows)
+{
+    const double M = stats[2 * blockIdx.y], Z = stats[2 * blockIdx.y + 1];
+    const int64_t w = (int64_t)blockIdx.y * n_rows;
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n_rows; r += (int64_t)gridDim.x * 256)
+        attn[w + r] = (float)(exp((double)scores[w + r] - M) / Z);
+}
+
+// dh[r, window's columns] = ds[window, r] * key[window's columns] (skipped when dh is NULL) and
+// partial[slot][C] = sum_r ds[window, r] * h[r, window's columns] over the block's slab, accumulated as
+// pool_colsum_kernel accumulates its masked sums
+template <typename T>
+__global__ __launch_bounds__(256) void attn_backward_kernel(const T *__restrict__ h, const float *__restrict__ ds,
+                                                            const float *__restrict__ key, T *__restrict__ dh,
+                                                            double *__restrict__ partial, int64_t n_rows, int C,
+                                                            int rows_per_block)
+{
+    constexpr int V = Lane<T>::V;
+    typedef typename Lane<T>::Raw Raw;
+    __shared__ double red[256 * V];
+    const Place p(C, V, n_rows, rows_per_block);
+    float kk[V];
+    double s[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        kk[i] = key[p.c0 + i];
+        s[i] = 0.0;
+    }
+    for (int64_t r = p.r0 + p.rl; r < p.r1; r += p.RL) {
+        const int64_t off = p.at(r);
+        const float d = ds[(int64_t)blockIdx.y * n_rows + r];
+        float x[V];
+        Lane<T>::unpack(*(const Raw *)(h + off), x);
+#pragma unroll
+        for (int i = 0; i < V; ++i) s[i] = fma((double)d, (double)x[i], s[i]);
+        if (dh != nullptr) {
+#pragma unroll
+            for (int i = 0; i < V; ++i) x[i] = d * kk[i];
+            *(Raw *)(dh + off) = Lane<T>::pack(x);
+        }
+    }
+    block_combine<V>(s, red, p, partial + p.slot() * C);
+}
+
 constexpr int64_t kBlocks = 2048;        // slabs of rows = partial rows (bwd_colsum_kernel's grid)
 constexpr int64_t kMaxBatch = 65535;     // windows ride on gridDim.y
 
@@ -679,6 +859,84 @@ int gcn_masked_broadcast(int dtype, const float *mask, const float *coef, void *
     else
         hipLaunchKernelGGL(pool_broadcast_kernel<bf16_t>, grid, block, 0, s, mask, coef, (bf16_t *)dh, n_rows,
                            (int)C, sl.rows_per_block);
+    return launched(who);
+}
+
+size_t gcn_attn_workspace_bytes(int64_t n_rows, int64_t C, int64_t batch, int dtype)
+{
+    if (n_rows < 1 || n_rows > (int64_t)INT32_MAX * kBlocks || !width_ok(C, dtype) || !batch_ok(batch)) return 0;
+    // scores: one (max, sum) pair per block; backward: one partial row [C] per block
+    return (size_t)batch * (size_t)Slabs(n_rows).blocks * (size_t)std::max<int64_t>(C, 2) * sizeof(double);
+}
+
+int gcn_attn_scores(int dtype, const void *h, const float *key, int64_t n_rows, int64_t C, int64_t batch,
+                    float *scores, double *stats, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *who = "gcn_attn_scores";
+    if (int rc = check_pool(who, dtype, n_rows, C, batch,
+                            h == nullptr || key == nullptr || scores == nullptr || stats == nullptr, (uintptr_t)h))
+        return rc;
+    if (workspace == nullptr || workspace_bytes < gcn_attn_workspace_bytes(n_rows, C, batch, dtype))
+        return bad(who, GCN_E_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace % 16 != 0 || (uintptr_t)stats % 8 != 0 || (uintptr_t)key % 4 != 0 ||
+        (uintptr_t)scores % 4 != 0)
+        return bad(who, GCN_E_ALIGN, "16-byte alignment required (stats: 8, key, scores: 4)");
+    const Slabs sl(n_rows);
+    const dim3 grid((unsigned)sl.blocks, (unsigned)batch), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    double *part = (double *)workspace;
+    if (dtype == GCN_DTYPE_F32)
+        hipLaunchKernelGGL(attn_scores_kernel<float>, grid, block, 0, s, (const float *)h, key, scores, part, n_rows,
+                           (int)C, sl.rows_per_block);
+    else
+        hipLaunchKernelGGL(attn_scores_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)h, key, scores, part,
+                           n_rows, (int)C, sl.rows_per_block);
+    hipLaunchKernelGGL(attn_finish_kernel, dim3((unsigned)batch), block, 0, s, (const double *)part, (int)sl.blocks,
+                       stats);
+    return launched(who);
+}
+
+int gcn_attn_normalize(const float *scores, const double *stats, float *attn, int64_t n_rows, int64_t batch,
+                       void *stream)
+{
+    const char *who = "gcn_attn_normalize";
+    if (n_rows < 1 || n_rows > (int64_t)INT32_MAX * kBlocks) return bad(who, GCN_E_BADARG, "needs n_rows >= 1");
+    if (!batch_ok(batch)) return bad(who, GCN_E_BADARG, "needs 1 <= batch <= 65535");
+    if (scores == nullptr || stats == nullptr || attn == nullptr) return bad(who, GCN_E_BADARG, "NULL pointer");
+    if ((uintptr_t)stats % 8 != 0 || (uintptr_t)scores % 4 != 0 || (uintptr_t)attn % 4 != 0)
+        return bad(who, GCN_E_ALIGN, "stats: 8-byte, scores, attn: 4-byte alignment required");
+    const dim3 grid((unsigned)std::min<int64_t>((n_rows + 255) / 256, 4096), (unsigned)batch);
+    hipLaunchKernelGGL(attn_normalize_kernel, grid, dim3(256), 0, (hipStream_t)stream, scores, stats, attn, n_rows);
+    return launched(who);
+}
+
+int gcn_attn_backward(int dtype, const void *h, const float *ds, const float *key, void *dh, double *dkey,
+                      int64_t n_rows, int64_t C, int64_t batch, void *workspace, size_t workspace_bytes,
+                      void *stream)
+{
+    const char *who = "gcn_attn_backward";
+    if (int rc = check_pool(who, dtype, n_rows, C, batch,
+                            h == nullptr || ds == nullptr || key == nullptr || dkey == nullptr,
+                            (uintptr_t)h | (uintptr_t)dh))
+        return rc;
+    if (workspace == nullptr || workspace_bytes < gcn_attn_workspace_bytes(n_rows, C, batch, dtype))
+        return bad(who, GCN_E_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace % 16 != 0 || (uintptr_t)dkey % 8 != 0 || (uintptr_t)key % 4 != 0 ||
+        (uintptr_t)ds % 4 != 0)
+        return bad(who, GCN_E_ALIGN, "16-byte alignment required (dkey: 8, key, ds: 4)");
+    const Slabs sl(n_rows);
+    const dim3 grid((unsigned)sl.blocks, (unsigned)batch), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    double *part = (double *)workspace;
+    if (dtype == GCN_DTYPE_F32)
+        hipLaunchKernelGGL(attn_backward_kernel<float>, grid, block, 0, s, (const float *)h, ds, key, (float *)dh,
+                           part, n_rows, (int)C, sl.rows_per_block);
+    else
+        hipLaunchKernelGGL(attn_backward_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)h, ds, key, (bf16_t *)dh,
+                           part, n_rows, (int)C, sl.rows_per_block);
+    hipLaunchKernelGGL(bn_finish_kernel<1>, finish_grid(C, batch), dim3(1024), 0, s, (const double *)part,
+                       (int)sl.blocks, (int)C, 1.0, 0.f, (const float *)nullptr, (float *)nullptr, (float *)nullptr,
+                       (float *)nullptr, dkey);
     return launched(who);
 }
 

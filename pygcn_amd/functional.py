@@ -17,6 +17,9 @@ if not __package__:   # flat import, the reference's convention (`from functiona
 from pygcn_amd.norm import relu_batch_norm  # noqa: E402,F401
 # the readout of its evaluator, PoolLayer (pygcn/models.py:267-286), for all samples at once: pygcn_amd/pool.py
 from pygcn_amd.pool import masked_mean_pool  # noqa: E402,F401
+# the head of its policy generator, SoftGeneratorPoolMLP's mean and SoftGeneratorAttention (pygcn/models.py:303-329):
+# pygcn_amd/attention.py
+from pygcn_amd.attention import vertex_attention, vertex_mean  # noqa: E402,F401
 
 
 class NLLGrad(torch.Tensor):

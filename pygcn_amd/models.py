@@ -7,6 +7,7 @@ Parameter names gc1.weight/bias, gc2.weight/bias as in the reference (models.py:
 import os
 import sys
 
+import torch
 import torch.nn as nn
 
 if not __package__:   # flat import, the reference's convention (`from models import GCN`)
@@ -14,6 +15,7 @@ if not __package__:   # flat import, the reference's convention (`from models im
     from layers import GraphConvolution
 else:
     from pygcn_amd.layers import GraphConvolution
+from pygcn_amd.attention import vertex_attention, vertex_mean  # noqa: E402
 from pygcn_amd.norm import relu_batch_norm  # noqa: E402
 from pygcn_amd.sharded import ShardedGraph  # noqa: E402
 from pygcn_amd.tuning import ROWGRAD_MIN_ROWS  # noqa: E402
@@ -166,3 +168,54 @@ class GCNBatchNorm(nn.Module):
         h = relu_batch_norm(self.gc2.forward_wide(h, adj, k), batch=k)
         out = self.gc3.forward_wide(h, adj, k, relu=True)
         return out.view(n, k, self.gc3.out_features).permute(1, 0, 2)
+
+
+class SoftGeneratorPoolMLP(nn.Module):
+    """The key MLP of the fork's SoftGenerator (reference pygcn/models.py:289-312) on the mean over the
+    vertices: linear1..linear3, ReLU after the first two, the result as wide as the input."""
+
+    def __init__(self, nin, nhid1, nhid2, bias=True):
+        super(SoftGeneratorPoolMLP, self).__init__()
+        self.linear1 = nn.Linear(nin, nhid1, bias=bias)
+        self.linear2 = nn.Linear(nhid1, nhid2, bias=bias)
+        self.linear3 = nn.Linear(nhid2, nin, bias=bias)
+
+    def forward(self, h):
+        x = vertex_mean(h)                                            # :304
+        x = torch.relu(self.linear1(x))
+        x = torch.relu(self.linear2(x))
+        return self.linear3(x)
+
+
+class SoftGenerator(nn.Module):
+    """The fork's policy generator (reference pygcn/models.py:412-433, `get_model(config, 'SoftGenerator')`):
+    the probability of picking each vertex,
+
+        h    = GCN(x[:, :dim_touched], adj)        three GraphConvolutions, ReLU after each   :428, :127-177
+        key  = PoolMLP(mean over vertices of h)    [1, nclass]                                :430, :303-312
+        attn = softmax over vertices of (h . key)  [N]                                        :431, :324-329
+
+    Submodule and parameter names are the fork's (GCN.gc1..gc3.{weight,bias}, PoolMLP.linear1..3.{weight,bias}),
+    so its checkpoints load.  The fork hard-codes PoolMLP's input width as 32, the value of its gcn_nclass;
+    here it is `nclass`.  `NN`, `dim_touched` and the plain lists `saved_log_probs` / `rewards` (the fork's
+    driver appends to them) are kept as attributes; its ReplayBuffer, the Categorical sampling and the
+    driver are not part of the model.  The mean and the attention run as HIP sweeps (pygcn_amd/attention.py);
+    `h` receives gradient from both, which autograd adds with one [N, nclass] addition."""
+
+    def __init__(self, nfeat, nhid, nclass, dropout, NN, linear_nhid1, linear_nhid2, dim_touched=None,
+                 linear_bias=True):
+        super(SoftGenerator, self).__init__()
+        self.GCN = GCNStack(nfeat, nhid, nclass, dropout, nlayers=3)
+        self.PoolMLP = SoftGeneratorPoolMLP(nclass, linear_nhid1, linear_nhid2, bias=linear_bias)
+        self.dim_touched = dim_touched
+        self.NN = NN
+        self.saved_log_probs = []
+        self.rewards = []
+
+    def forward(self, x, adj):
+        if isinstance(adj, ShardedGraph):
+            raise RuntimeError("SoftGenerator: a ShardedGraph adjacency is not supported — the softmax and the "
+                               "mean run over all vertices, and cross-rank reductions are not built")
+        h = self.GCN(x[:, :self.dim_touched].contiguous(), adj)     # (a copy only if the slice drops columns)
+        key = self.PoolMLP(h)
+        return vertex_attention(h, key)
