@@ -82,7 +82,9 @@ typedef struct gcn_csr_plan {
  * pygcn/models.py:267-286); the existing gcn_bn_ entry points are now the batch = 1 launch of the same kernels,
  * with the same results.  Also additive to 26: the vertex-attention sweeps gcn_attn_workspace_bytes /
  * gcn_attn_scores / gcn_attn_normalize / gcn_attn_backward (the head of its SoftGenerator, reference
- * pygcn/models.py:324-329).
+ * pygcn/models.py:324-329).  Also additive to 26: vertex selection, gcn_select_workspace_bytes / gcn_select_kth /
+ * gcn_select_indices / gcn_topk_flag / gcn_race_keys (the end of its Generator, Hierarchical_Generator and of
+ * SoftGenerator's policy step, reference pygcn/models.py:373-377, rl-policy-generator.py:324-336).
  * 25 (round 4, late): new entry point gcn_gemm_atg256_f32_b3_colsum (the
  * weight gradient with the bias gradient Σ G[rows] as a side result); gcn_gemm_atg256_workspace_bytes grew by
  * 1 KiB per workgroup; struct gcn_gemm_epilogue gained keep_bits_out / mask_bits at its END (zero them);
@@ -685,6 +687,61 @@ int gcn_attn_normalize(const float *scores, const double *stats, float *attn, in
 int gcn_attn_backward(int dtype, const void *h, const float *ds, const float *key, void *dh, double *dkey,
                       int64_t n_rows, int64_t C, int64_t batch, void *workspace, size_t workspace_bytes,
                       void *stream);
+
+/*
+ * Vertex selection over the same per-vertex layout — how every policy generator of the fork ends: the top-NN
+ * flag of Generator / Hierarchical_Generator (reference pygcn/models.py:373-377, :398-406: argsort, compare
+ * with the score at index NN) and SoftGenerator's draw of NN vertices without replacement (reference
+ * pygcn/rl-policy-generator.py:324-336: torch.multinomial + .tolist()).  Every per-vertex vector (keys, s,
+ * flag, p) is fp32 [batch, n_rows], contiguous, one window's rows consecutive; 1 <= n_rows < 2^31,
+ * 1 <= batch <= 65535 (else GCN_E_BADARG).  Nothing is read back by the host.
+ *
+ * ORDER.  All selection uses one total order on fp32: -0 is +0; every NaN (any sign, any payload) is greater
+ * than +inf, which is where torch.argsort(descending=True) places it; otherwise the numeric order.  (The
+ * order-preserving uint32: all bits of a negative flipped, the sign bit of a non-negative set, NaN 0xFFFFFFFF.)
+ *
+ *   gcn_select_kth      thr[j] = the kth-largest key of window j in that order (kth 1-based, 1 <= kth <= n_rows;
+ *                       a NaN comes back as 0x7FC00000 and a zero as +0) and count_gt[j] = the number of keys
+ *                       strictly greater; DEVICE fp32 [batch] and int32 [batch].  A radix select over 11 / 11 /
+ *                       10 bits from the top: seven launches — one that zeroes the scratch, then per digit a
+ *                       read sweep whose blocks count the keys that match the digits found so far in LDS bins
+ *                       (integer atomics) and add them to the window's bins (integer atomics), and a one-block
+ *                       step that picks the digit and carries prefix, remaining rank and count in the scratch.
+ *   gcn_select_indices  idx[j, 0 .. m) (DEVICE int64 [batch, m], 8-byte aligned, 1 <= m <= n_rows) = the
+ *                       vertices whose key is greater than thr[j], plus the lowest-index vertices whose key
+ *                       equals it, until there are m; ascending vertex order.  thr and count_gt are
+ *                       gcn_select_kth's results for kth = m (other values write only inside idx and may
+ *                       leave slots unwritten).  Three launches: count per block, scan, write.
+ *   gcn_topk_flag       flag[j, r] = s[j, r] > thr[j] ? s[j, r] * (1.0f / s[j, r]) : 0 with the ordinary float
+ *                       comparison (a NaN score or threshold selects nothing); quotient and product are each
+ *                       rounded to fp32 once, IEEE: the bits of `s * torch.reciprocal(s)`, 0 * inf = NaN
+ *                       included.  An unselected vertex gets +0 whatever its score (the fork's `s * 0` leaves
+ *                       NaN for a NaN or infinite score).  flag may alias s.
+ *   gcn_race_keys       the keys of an exponential race: the m largest of p_r / E_r, E_r i.i.d. Exp(1), are m
+ *                       draws without replacement with probabilities proportional to p.  For vertex r of window j
+ *                           w   = Philox4x32-10(counter = (q_lo, q_hi, j, 1), key = (seed_lo, seed_hi)),  q = r >> 2
+ *                           u   = (w[r & 3] + 0.5) * 2^-32          in double (exact)
+ *                           E   = -log(u)                           in double; 1.16e-10 <= E <= 22.9
+ *                           key = (float)((double)p / E)            rounded once
+ *                       (the dropout stream has counter word 3 = 0: one seed never gives both the same bits).
+ *                       p = 0 gives key +0: such a vertex is taken after every positive one, lowest index first.
+ *                       A negative or non-finite p is the CALLER'S ERROR and is not detected (torch.multinomial
+ *                       raises, which needs a host read).  keys may alias p.
+ * Integer atomics and fixed-order scans only: two runs give the same bytes, and window j of a batched call is,
+ * bit for bit, the batch = 1 call on a contiguous copy of the window.  Tensors 4-byte aligned (GCN_E_ALIGN).
+ * Scratch of gcn_select_kth and gcn_select_indices, which the caller need not initialise:
+ *     gcn_select_workspace_bytes = batch * (3 * 2048 + 8 + 2 * B) * sizeof(int32_t),  B = min(ceil(n_rows / 1024), 1024);
+ * block b of a window sweeps rows [b * R, min((b + 1) * R, n_rows)), R = ceil(n_rows / B), 256 rows per
+ * iteration.  0 outside the rule; a short or NULL workspace is GCN_E_WORKSPACE.
+ * (ABI 26, additive.)
+ */
+size_t gcn_select_workspace_bytes(int64_t n_rows, int64_t batch);
+int gcn_select_kth(const float *keys, int64_t n_rows, int64_t batch, int64_t kth, float *thr, int32_t *count_gt,
+                   void *workspace, size_t workspace_bytes, void *stream);
+int gcn_select_indices(const float *keys, int64_t n_rows, int64_t batch, int64_t m, const float *thr,
+                       const int32_t *count_gt, int64_t *idx, void *workspace, size_t workspace_bytes, void *stream);
+int gcn_topk_flag(const float *s, int64_t n_rows, int64_t batch, const float *thr, float *flag, void *stream);
+int gcn_race_keys(const float *p, int64_t n_rows, int64_t batch, uint64_t seed, float *keys, void *stream);
 
 #ifdef __cplusplus
 }

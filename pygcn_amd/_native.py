@@ -125,6 +125,11 @@ SIGNATURES = {
     "gcn_attn_scores": (i, [i, p, p, i64, i64, i64, p, p, p, sz, p]),
     "gcn_attn_normalize": (i, [p, p, p, i64, i64, p]),
     "gcn_attn_backward": (i, [i, p, p, p, p, p, i64, i64, i64, p, sz, p]),
+    "gcn_select_workspace_bytes": (sz, [i64, i64]),
+    "gcn_select_kth": (i, [p, i64, i64, i64, p, p, p, sz, p]),
+    "gcn_select_indices": (i, [p, i64, i64, i64, p, p, p, p, sz, p]),
+    "gcn_topk_flag": (i, [p, i64, i64, p, p, p]),
+    "gcn_race_keys": (i, [p, i64, i64, ctypes.c_uint64, p, p]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -120,4 +120,6 @@ def vertex_mean(h):
     if _wide_storage(h) is None:
         return h.mean(-2, keepdim=h.dim() == 2)
     ones = torch.ones(h.shape[:-1], dtype=torch.float32, device=h.device)
-    return masked_mean_pool(h, ones, count=h.shape[-2])
+    # (the count as a tensor FILLED on the device: a Python number would reach it by a host-to-device copy,
+    #  which synchronises the stream)
+    return masked_mean_pool(h, ones, count=torch.full((1,), float(h.shape[-2]), dtype=torch.float32, device=h.device))

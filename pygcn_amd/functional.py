@@ -20,6 +20,9 @@ from pygcn_amd.pool import masked_mean_pool  # noqa: E402,F401
 # the head of its policy generator, SoftGeneratorPoolMLP's mean and SoftGeneratorAttention (pygcn/models.py:303-329):
 # pygcn_amd/attention.py
 from pygcn_amd.attention import vertex_attention, vertex_mean  # noqa: E402,F401
+# how its policy generators end — the top-NN flag (pygcn/models.py:373-377) and the draw of NN vertices without
+# replacement with its log-probability (pygcn/rl-policy-generator.py:324-336): pygcn_amd/select.py
+from pygcn_amd.select import sample_without_replacement, selection_log_prob, topk_flag  # noqa: E402,F401
 
 
 class NLLGrad(torch.Tensor):

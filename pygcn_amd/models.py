@@ -17,6 +17,7 @@ else:
     from pygcn_amd.layers import GraphConvolution
 from pygcn_amd.attention import vertex_attention, vertex_mean  # noqa: E402
 from pygcn_amd.norm import relu_batch_norm  # noqa: E402
+from pygcn_amd.select import sample_without_replacement, selection_log_prob, topk_flag  # noqa: E402
 from pygcn_amd.sharded import ShardedGraph  # noqa: E402
 from pygcn_amd.tuning import ROWGRAD_MIN_ROWS  # noqa: E402
 
@@ -198,9 +199,13 @@ class SoftGenerator(nn.Module):
     Submodule and parameter names are the fork's (GCN.gc1..gc3.{weight,bias}, PoolMLP.linear1..3.{weight,bias}),
     so its checkpoints load.  The fork hard-codes PoolMLP's input width as 32, the value of its gcn_nclass;
     here it is `nclass`.  `NN`, `dim_touched` and the plain lists `saved_log_probs` / `rewards` (the fork's
-    driver appends to them) are kept as attributes; its ReplayBuffer, the Categorical sampling and the
-    driver are not part of the model.  The mean and the attention run as HIP sweeps (pygcn_amd/attention.py);
-    `h` receives gradient from both, which autograd adds with one [N, nclass] addition."""
+    driver appends to them) are kept as attributes; its ReplayBuffer and the driver are not part of the
+    model.  The mean and the attention run as HIP sweeps (pygcn_amd/attention.py); `h` receives gradient
+    from both, which autograd adds with one [N, nclass] addition.
+
+    The policy step of the fork's driver is here as two methods over pygcn_amd/select.py: `select_action`
+    (its `select_action`, reference pygcn/rl-policy-generator.py:324-370) and `log_prob` (its
+    ReplayBuffer.get_log_prob, pygcn/utils.py:516-522), neither with a host synchronisation."""
 
     def __init__(self, nfeat, nhid, nclass, dropout, NN, linear_nhid1, linear_nhid2, dim_touched=None,
                  linear_bias=True):
@@ -219,3 +224,123 @@ class SoftGenerator(nn.Module):
         h = self.GCN(x[:, :self.dim_touched].contiguous(), adj)     # (a copy only if the slice drops columns)
         key = self.PoolMLP(h)
         return vertex_attention(h, key)
+
+    def select_action(self, x, adj, seed=None):
+        """The fork's `select_action` (reference pygcn/rl-policy-generator.py:324-370): attn = self(x, adj), NN
+        vertices drawn without replacement with probabilities attn, the sum of their Categorical
+        log-probabilities appended to `saved_log_probs`, and the result `(vac_flag, idx)` — vac_flag the
+        zeros of attn's shape with ones at the picks (its reset_vac_flag), idx the int64 [NN] picks in draw
+        order ON THE DEVICE, where the fork holds a Python list after `.tolist()`.  `seed` as in
+        `functional.sample_without_replacement`."""
+        attn = self(x, adj)
+        idx = sample_without_replacement(attn, self.NN, seed=seed)
+        self.saved_log_probs.append(selection_log_prob(attn, idx))
+        vac_flag = torch.zeros_like(attn.detach()).scatter_(0, idx, 1.0)
+        return vac_flag, idx
+
+    def log_prob(self, x, adj, idx):
+        """The fork's ReplayBuffer.get_log_prob (reference pygcn/utils.py:516-522): the summed Categorical
+        log-probability of the picks `idx` (int64 tensor or list) under the CURRENT parameters."""
+        attn = self(x, adj)
+        idx = torch.as_tensor(idx, dtype=torch.int64, device=attn.device)
+        return selection_log_prob(attn, idx)
+
+
+class MLPLayers(nn.Module):
+    """The fork's MLPLayers (reference pygcn/models.py:195-217): linear1..linear3, ReLU after the first two."""
+
+    def __init__(self, nin, nhid1, nhid2, nout=1, bias=True):
+        super(MLPLayers, self).__init__()
+        self.linear1 = nn.Linear(nin, nhid1, bias=bias)
+        self.linear2 = nn.Linear(nhid1, nhid2, bias=bias)
+        self.linear3 = nn.Linear(nhid2, nout, bias=bias)
+
+    def forward(self, x):
+        x = torch.relu(self.linear1(x))
+        x = torch.relu(self.linear2(x))
+        return self.linear3(x)
+
+
+class GeneratorMLPLayers(nn.Module):
+    """The fork's GeneratorMLPLayers (reference pygcn/models.py:220-241): linear1..linear3 with
+    `apply_bn(F.relu(.))` after the first two — ReLU + BatchNorm as the HIP sweeps of pygcn_amd/norm.py
+    where the width obeys their shape rule.  The fork builds a FRESH BatchNorm1d on every call (:228-232), so
+    there is no learned or running state and batch statistics are used under `eval()` too, as GCNBatchNorm
+    documents."""
+
+    def __init__(self, nin, nhid1, nhid2, nout=1, bias=True):
+        super(GeneratorMLPLayers, self).__init__()
+        self.linear1 = nn.Linear(nin, nhid1, bias=bias)
+        self.linear2 = nn.Linear(nhid1, nhid2, bias=bias)
+        self.linear3 = nn.Linear(nhid2, nout, bias=bias)
+
+    def forward(self, x):
+        x = relu_batch_norm(self.linear1(x))                 # :235
+        x = relu_batch_norm(self.linear2(x))                 # :236
+        return self.linear3(x)
+
+
+class Generator(nn.Module):
+    """The fork's Generator (reference pygcn/models.py:358-379, `get_model(config, 'Generator')`): a 0/1 flag
+    on the NN vertices with the largest score,
+
+        h      = GCNLayer(x[:, :dim_touched], adj)           three GraphConvolutions, ReLU after each  :368, :74-124
+        score  = MLPLayers(cat(h, x[:, dim_touched:]))       [N, 1], ReLU + BatchNorm inside           :369-370
+        flag   = score * where(score > score[argsort(score)[NN]], 1 / score, 0)                       :373-377
+
+    The last three lines are `functional.topk_flag`: a radix select instead of the sort, no host
+    synchronisation.  The fork's `print` of four `.item()` values of the scores (:371) — four host
+    synchronisations per call — is dropped.  Submodule and parameter names are the fork's
+    (GCNLayer.gc1..gc3, MLPLayers.linear1..linear3), so its checkpoints load; `linear_nin` must be
+    nclass + (columns of x past dim_touched)."""
+
+    def __init__(self, nfeat, nhid, nclass, dropout, NN, linear_nin, linear_nhid1, linear_nhid2, dim_touched=None,
+                 linear_nout=1, linear_bias=True):
+        super(Generator, self).__init__()
+        self.GCNLayer = GCNStack(nfeat, nhid, nclass, dropout, nlayers=3)
+        self.MLPLayers = GeneratorMLPLayers(linear_nin, linear_nhid1, linear_nhid2, linear_nout, bias=linear_bias)
+        self.dim_touched = dim_touched
+        self.NN = NN
+
+    def scores(self, x, adj):
+        """The per-vertex score [N, 1] the flag is taken from (the fork's `mlp_output`)."""
+        if isinstance(adj, ShardedGraph):
+            raise RuntimeError("Generator: a ShardedGraph adjacency is not supported — the selection and the "
+                               "BatchNorm statistics run over all vertices, and cross-rank reductions are not built")
+        d = x.shape[1] if self.dim_touched is None else self.dim_touched
+        h = self.GCNLayer(x[:, :d].contiguous(), adj)
+        return self.MLPLayers(torch.cat((h, x[:, d:]), dim=1))
+
+    def forward(self, x, adj):
+        return topk_flag(self.scores(x, adj), self.NN)
+
+
+class Hierarchical_Generator(nn.Module):
+    """The fork's Hierarchical_Generator (reference pygcn/models.py:382-408): Generator over the plain
+    MLPLayers, where the LAST column of x is a group label that does not enter the MLP (:392) and every
+    vertex of `target_group` (0, as the fork hard-codes it, :394) gets the minimum score before the flag
+    is taken (:395-397) — torch ops on [N], the minimum stays on the device."""
+
+    target_group = 0
+
+    def __init__(self, nfeat, nhid, nclass, dropout, NN, linear_nin, linear_nhid1, linear_nhid2, dim_touched=None,
+                 linear_nout=1, linear_bias=True):
+        super(Hierarchical_Generator, self).__init__()
+        self.GCNLayer = GCNStack(nfeat, nhid, nclass, dropout, nlayers=3)
+        self.MLPLayers = MLPLayers(linear_nin, linear_nhid1, linear_nhid2, linear_nout, bias=linear_bias)
+        self.dim_touched = dim_touched
+        self.NN = NN
+
+    def scores(self, x, adj):
+        """The masked per-vertex score [N, 1] the flag is taken from."""
+        if isinstance(adj, ShardedGraph):
+            raise RuntimeError("Hierarchical_Generator: a ShardedGraph adjacency is not supported — the selection "
+                               "runs over all vertices, and cross-rank reductions are not built")
+        d = x.shape[1] - 1 if self.dim_touched is None else self.dim_touched
+        h = self.GCNLayer(x[:, :d].contiguous(), adj)
+        mlp_output = self.MLPLayers(torch.cat((h, x[:, d:-1]), dim=1))
+        min_value = (torch.ones_like(mlp_output) * torch.min(mlp_output)).squeeze(1)
+        return torch.where(x[:, -1] == self.target_group, min_value, mlp_output.squeeze(1)).unsqueeze(1)
+
+    def forward(self, x, adj):
+        return topk_flag(self.scores(x, adj), self.NN)
