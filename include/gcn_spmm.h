@@ -84,7 +84,9 @@ typedef struct gcn_csr_plan {
  * gcn_attn_scores / gcn_attn_normalize / gcn_attn_backward (the head of its SoftGenerator, reference
  * pygcn/models.py:324-329).  Also additive to 26: vertex selection, gcn_select_workspace_bytes / gcn_select_kth /
  * gcn_select_indices / gcn_topk_flag / gcn_race_keys (the end of its Generator, Hierarchical_Generator and of
- * SoftGenerator's policy step, reference pygcn/models.py:373-377, rl-policy-generator.py:324-336).
+ * SoftGenerator's policy step, reference pygcn/models.py:373-377, rl-policy-generator.py:324-336).  Also additive to
+ * 26: the input side of its evaluator, gcn_eval_workspace_bytes / gcn_eval_ingest / gcn_eval_ingest_backward
+ * (GCN_OVER_MLP and PoolLayer, reference pygcn/models.py:333-355, :267-286).
  * 25 (round 4, late): new entry point gcn_gemm_atg256_f32_b3_colsum (the
  * weight gradient with the bias gradient Σ G[rows] as a side result); gcn_gemm_atg256_workspace_bytes grew by
  * 1 KiB per workgroup; struct gcn_gemm_epilogue gained keep_bits_out / mask_bits at its END (zero them);
@@ -742,6 +744,52 @@ int gcn_select_indices(const float *keys, int64_t n_rows, int64_t batch, int64_t
                        const int32_t *count_gt, int64_t *idx, void *workspace, size_t workspace_bytes, void *stream);
 int gcn_topk_flag(const float *s, int64_t n_rows, int64_t batch, const float *thr, float *flag, void *stream);
 int gcn_race_keys(const float *p, int64_t n_rows, int64_t batch, uint64_t seed, float *keys, void *stream);
+
+/*
+ * The input side of the fork's evaluator GCN_OVER_MLP (reference pygcn/models.py:333-355, PoolLayer :267-286) as one
+ * read sweep of x and one write sweep of dx.  x is a contiguous fp32 [batch, n_rows, F] tensor, sample after
+ * sample, as the fork holds it (reference pygcn/gnn-over-mlp.py:219-237, F = 9 or 17): the columns [0, d) feed the
+ * GCN (d = its dim_touched), the e = F - 1 - d columns [d, F-1) are pooled as they are, and the last column is the
+ * 0/1 vertex flag the pool multiplies by and counts.  m(j, n) is flag[j, n] when `flag` (contiguous fp32
+ * [batch, n_rows]) is not NULL, and x[j, n, F-1] otherwise.
+ *   gcn_eval_ingest           one read of x (and flag); every output pointer may be NULL, that output is skipped:
+ *       wide[n, j * d + c]   = x[j, n, c], c < d          fp32 [n_rows, batch * d], the layout the batched layers
+ *                                                         keep (k samples side by side); a pure copy
+ *       mask[j, n]           = m(j, n)                    fp32 [batch, n_rows], the layout gcn_masked_colsum reads
+ *       esum[j * e + c - d]  = sum_n m(j, n) * x[j, n, c], d <= c < F-1     DEVICE double [batch * e], 8-byte
+ *                              aligned: products and sums are carried in double per thread, per block and in a
+ *                              finish launch, added in a fixed order — no float atomics, bitwise reproducible.
+ *                              The mask MULTIPLIES (0 * NaN = NaN, as in the fork).
+ *       nonzero[j]           = #{n : m(j, n) != 0}        DEVICE int64 [batch], 8-byte aligned; a NaN counts, as
+ *                              torch.nonzero counts it; integer adds only.
+ *   gcn_eval_ingest_backward  one sweep: reads x (and flag), d_wide [n_rows, batch * d], d_mask [batch, n_rows] and
+ *                             d_esum fp32 [batch * e] — each of the three gradients may be NULL, which means zero —
+ *                             and writes dx [batch, n_rows, F]:
+ *       dx[j, n, c < d]        = d_wide[n, j * d + c]
+ *       dx[j, n, d <= c < F-1] = m(j, n) * d_esum[j * e + c - d]          one fp32 product, rounded once
+ *       dm(j, n)               = d_mask[j, n] + sum_c x[j, n, c] * d_esum[j * e + c - d]    in double, rounded once
+ *                             Without `flag`, dm goes to dx[j, n, F-1].  With `flag`, dm goes to dflag[j, n] (fp32
+ *                             [batch, n_rows]; may be NULL) and dx[j, n, F-1] = 0.  dx may be NULL when flag and
+ *                             dflag are given: the sweep then reads only the columns >= d of x and writes
+ *                             batch * n_rows floats.  dflag without flag, or neither dx nor dflag, is GCN_E_BADARG.
+ * Both sweeps stage tiles of 64 consecutive vertices x as many samples as fit 32 KiB through LDS (a block may take a
+ * sub-range of the samples, on gridDim.y), so that every global access is a run of consecutive dwords: of a sample's
+ * flat array on the x / dx side, of a row of wide / d_wide on the other, of one sample's mask.
+ * SHAPE RULE: n_rows >= 1, 2 <= F <= 64, 0 <= d <= F - 1, 1 <= batch <= 65535 (else GCN_E_BADARG); x NULL is
+ * GCN_E_BADARG.  Every fp32 tensor 4-byte aligned, esum and nonzero 8-byte, the workspace 16-byte (GCN_E_ALIGN).
+ * Scratch of gcn_eval_ingest, needed when esum or nonzero is asked for (short or NULL: GCN_E_WORKSPACE):
+ *     gcn_eval_workspace_bytes = B * batch * (F - d) * sizeof(double),  B = min(ceil(n_rows / 64), 2048)
+ * — per block batch * e partial sums and batch partial counts; block b sweeps the rows [b * R, min((b + 1) * R,
+ * n_rows)), R = 64 * ceil(n_rows / (64 * B)), in tiles of 64.  0 outside the rule.
+ * (ABI 26, additive.)
+ */
+size_t gcn_eval_workspace_bytes(int64_t n_rows, int64_t F, int64_t d, int64_t batch);
+int gcn_eval_ingest(const float *x, const float *flag, int64_t n_rows, int64_t F, int64_t d, int64_t batch,
+                    float *wide, float *mask, double *esum, int64_t *nonzero, void *workspace,
+                    size_t workspace_bytes, void *stream);
+int gcn_eval_ingest_backward(const float *x, const float *flag, const float *d_wide, const float *d_mask,
+                             const float *d_esum, int64_t n_rows, int64_t F, int64_t d, int64_t batch, float *dx,
+                             float *dflag, void *stream);
 
 #ifdef __cplusplus
 }

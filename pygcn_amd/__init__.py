@@ -10,9 +10,9 @@ from .graph import CSRGraph, as_graph
 from .spmm import spmm_csr
 from .ops import sparse_mm          # also registers torch.ops.pygcn_amd.spmm_csr
 from .layers import GraphConvolution
-from .models import GCN, GCNBatchNorm, Generator, Hierarchical_Generator, SoftGenerator
+from .models import GCN, GCNBatchNorm, GCN_OVER_MLP, Generator, Hierarchical_Generator, SoftGenerator, get_model
 
 # `pygcn_amd.spmm` is the MODULE (kernels' Python launchers + autograd nodes); the drop-in for
 # `torch.spmm` / `torch.sparse.mm` is exported as `sparse_mm`.
 __all__ = ["CSRGraph", "as_graph", "sparse_mm", "spmm_csr", "GraphConvolution", "GCN", "GCNBatchNorm",
-           "Generator", "Hierarchical_Generator", "SoftGenerator"]
+           "GCN_OVER_MLP", "Generator", "Hierarchical_Generator", "SoftGenerator", "get_model"]

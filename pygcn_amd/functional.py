@@ -23,6 +23,9 @@ from pygcn_amd.attention import vertex_attention, vertex_mean  # noqa: E402,F401
 # how its policy generators end — the top-NN flag (pygcn/models.py:373-377) and the draw of NN vertices without
 # replacement with its log-probability (pygcn/rl-policy-generator.py:324-336): pygcn_amd/select.py
 from pygcn_amd.select import sample_without_replacement, selection_log_prob, topk_flag  # noqa: E402,F401
+# the input side of its evaluator GCN_OVER_MLP (pygcn/models.py:341-355) — the GCN's columns side by side, the
+# flag as the pool's mask, the untouched columns' masked sums, the flag's count — in one sweep: pygcn_amd/evaluator.py
+from pygcn_amd.evaluator import evaluator_ingest  # noqa: E402,F401
 
 
 class NLLGrad(torch.Tensor):

@@ -11,6 +11,7 @@ storage, read in place:
 
     forward    gcn_masked_colsum      reads h            -> double [k*C] sums (fixed order, reproducible)
     backward   gcn_masked_broadcast   writes dh = mask[j, n] * (g[j, c] / count[j])
+               gcn_attn_scores        (mask_grad=True only) reads h -> dmask[j, n] = sum_c h[j, n, c] * g[j, c] / count[j]
 
 The division by the count and the [k*C] coefficient vector are torch ops on [k, C] tensors; nothing
 synchronises with the host.
@@ -57,11 +58,24 @@ def masked_broadcast(mask_kn, coef, n, k, c, dtype):
     return dh
 
 
+def masked_rowdot(h, coef, n, k, c):
+    """fp32 [k, n]: sum_c h[r, j*C + c] * coef[j*C + c] over storage [n, k*C] starting at h.data_ptr() — the
+    per-vertex dot product of the attention scores (gcn_attn_scores with key = coef; its softmax statistics
+    are not used)."""
+    dt = _DTYPES[h.dtype]
+    dots = torch.empty((k, n), dtype=torch.float32, device=h.device)
+    stats = torch.empty((k, 2), dtype=torch.float64, device=h.device)
+    _native.launch("gcn_attn_scores", h.device, dt, h.data_ptr(), coef.data_ptr(), n, c, k, dots.data_ptr(),
+                   stats.data_ptr(), workspace=_native.lib().gcn_attn_workspace_bytes(n, c, k, dt))
+    return dots
+
+
 class MaskedMeanPoolFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, h, mask_kn, count, n, k, c):
+    def forward(ctx, h, mask_kn, count, n, k, c, mask_grad=False):
         ctx.dims, ctx.h_dim = (n, k, c), h.dim()
-        ctx.save_for_backward(mask_kn, count)
+        ctx.mask_grad = bool(mask_grad)
+        ctx.save_for_backward(mask_kn, count, *([h] if mask_grad else []))
         ctx.set_materialize_grads(True)
         sums = masked_colsum(h, mask_kn, n, k, c).view(k, c)
         return (sums / count.double().view(-1, 1)).to(h.dtype)
@@ -69,15 +83,20 @@ class MaskedMeanPoolFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        mask_kn, count = ctx.saved_tensors
+        mask_kn, count = ctx.saved_tensors[:2]
         n, k, c = ctx.dims
         coef = (g.float() / count.view(-1, 1)).contiguous().view(k * c)
-        dh = masked_broadcast(mask_kn, coef, n, k, c, g.dtype)
-        dh = dh if ctx.h_dim == 2 else dh.view(n, k, c).permute(1, 0, 2)
-        return dh, None, None, None, None, None
+        dh = None
+        if ctx.needs_input_grad[0]:
+            dh = masked_broadcast(mask_kn, coef, n, k, c, g.dtype)
+            dh = dh if ctx.h_dim == 2 else dh.view(n, k, c).permute(1, 0, 2)
+        dmask = None
+        if ctx.mask_grad and ctx.needs_input_grad[1]:
+            dmask = masked_rowdot(ctx.saved_tensors[2], coef, n, k, c)          # fp32 [k, N], as mask_kn
+        return dh, dmask, None, None, None, None, None
 
 
-def masked_mean_pool(h, mask, count=None):
+def masked_mean_pool(h, mask, count=None, mask_grad=False):
     """`(h * mask[:, :, None]).sum(1) / count[:, None]` -> [k, C]: the fork's PoolLayer (reference
     pygcn/models.py:267-286) for all k samples at once.
 
@@ -87,11 +106,16 @@ def masked_mean_pool(h, mask, count=None):
     `count=(mask[0] != 0).sum()`.  The mask multiplies (a NaN under a zero mask stays NaN), a zero
     count gives what torch's division gives, `mask` and `count` get no gradient.
 
+    `mask_grad=True`: the mask is an input like `h` and receives sum_c h[j, n, c] * g[j, c] / count[j] — what
+    the fork's evaluator hands back to a generator through the vertex flag (reference
+    pygcn/policy-generator.py:398-420).  `count` never gets a gradient.
+
     On the HIP device, for fp32 / bf16 `h` that is the [k, N, C] permuted view of contiguous [N, k*C]
     storage (what GCNBatchNorm returns for a batched input) or a contiguous [N, C] tensor, with C a
     multiple of the 16-byte lane width v (4 fp32 / 8 bf16) and C/v dividing 256, this is one autograd
-    node over two HIP sweeps that read `h` in place; any other layout, width or device takes the torch
-    composition above."""
+    node over two HIP sweeps that read `h` in place (with `mask_grad`, a third: the per-vertex dot product
+    of gcn_attn_scores with key = g / count); any other layout, width or device takes the torch composition
+    above."""
     if h.dim() == 2:
         if mask.dim() != 1:
             raise RuntimeError("masked_mean_pool: h [N, C] takes mask [N]")
@@ -99,9 +123,10 @@ def masked_mean_pool(h, mask, count=None):
     if h.dim() not in (2, 3) or mask.dim() != 2 or tuple(mask.shape) != ((1,) if h.dim() == 2 else (h.shape[0],)) \
             + (h.shape[-2],):
         raise RuntimeError(f"masked_mean_pool: h {tuple(h.shape)} does not go with mask {tuple(mask.shape)}")
-    mask = mask.detach()
+    if not mask_grad:
+        mask = mask.detach()
     if count is None:
-        count = (mask != 0).sum(1)
+        count = (mask.detach() != 0).sum(1)
     count = torch.as_tensor(count, device=h.device).detach()
     dims = _wide_storage(h) if mask.device == h.device else None
     if dims is None:
@@ -110,4 +135,6 @@ def masked_mean_pool(h, mask, count=None):
     n, k, c = dims
     mask_kn = mask.to(torch.float32).contiguous()                    # [k, N] as given: k*N floats, no transpose
     count = count.to(torch.float32).reshape(-1).expand(k).contiguous()
+    if mask_grad:
+        return MaskedMeanPoolFunction.apply(h, mask_kn, count, n, k, c, True)
     return MaskedMeanPoolFunction.apply(h, mask_kn, count, n, k, c)
