@@ -393,6 +393,10 @@ int gcn_row_normalize_device(const void *rowptr, int rowptr_is64, float *val, in
  * configs C3/C4.  fp32 in / out / accumulate; operands are split into three bf16 parts on the
  * fly and multiplied with six bf16 MFMAs (fp32-level accuracy, see gcn_gemm.hip).  DEVICE
  * pointers; X rows 16-byte aligned; workspace >= gcn_gemm_xw256_workspace_bytes() (384 KiB).
+ * W (here and in gcn_gemm_xw256_f32_h2 / _b3 / gcn_gemm_xw_bf16) needs no more than its element's
+ * alignment and any ldw >= its width: a prep kernel reads it element by element into the workspace.
+ * ldx, ldy (and ld_mask) >= the width, multiples of 16 bytes (GCN_E_ALIGN); nothing outside the M x
+ * width window of Y is written (tests/test_gemm_exact_gpu.py).
  */
 size_t gcn_gemm_xw256_workspace_bytes(void);
 int gcn_gemm_xw256_f32(const float *X, int64_t ldx, const float *W, int64_t ldw, float *Y, int64_t ldy,
