@@ -795,6 +795,44 @@ int gcn_eval_ingest_backward(const float *x, const float *flag, const float *d_w
                              const float *d_esum, int64_t n_rows, int64_t F, int64_t d, int64_t batch, float *dx,
                              float *dflag, void *stream);
 
+/*
+ * The per-vertex score head of the fork's Generator and Hierarchical_Generator (reference pygcn/models.py:368-370,
+ * :391-393, the two MLPs :195-241) as fused sweeps that recompute the hidden activations instead of storing them:
+ *     score[n] = linear3( bn(relu( linear2( bn(relu( linear1( cat(h[n, :], x[n, d : d + T]) ))) )) ))
+ * h fp32 [n_rows, C] contiguous; x fp32 with row pitch ldx floats, of which only the columns [d, d + T) are read
+ * (the concatenation never exists; x may be NULL when T = 0); W1 [H1, C + T], W2 [H2, H1], W3 [1, H2] in the
+ * nn.Linear layout; the biases b1 [H1], b2 [H2], b3 [1] may each be NULL (zero).  batch_norm != 0: after each ReLU
+ * the fork's FRESH BatchNorm1d — batch statistics over all n_rows, biased variance, eps 1e-5, gamma 1, beta 0;
+ * batch_norm = 0: the plain MLPLayers.
+ *   forward   scores fp32 [n_rows].  stats fp32 [4 * 64] (mean1, rstd1, mean2, rstd2 at pitch 64; written with
+ *             batch_norm, else untouched and may be NULL) — what the backward call reads.  mask1, mask2: int64
+ *             [n_rows], both or neither (NULL): bit j set when column j of that hidden layer counted as > 0.
+ *             3 sweeps with batch_norm (statistics of layer 1, of layer 2, the score), 1 without.
+ *   backward  dscores fp32 [n_rows] -> dh fp32 [n_rows, C] and the parameter gradients in the parameters' layouts;
+ *             dh and each of the six may be NULL (skipped).  3 sweeps with batch_norm, 1 without.
+ * Column sums are carried in double, the weight-gradient outer products in fp32 per wave over its slab of rows; one
+ * partial row per block, added in a fixed order in double by a finish launch: no float atomics, bitwise
+ * reproducible.  Nothing allocates or synchronises; capturable.
+ * SHAPE RULE: n_rows >= 64, 1 <= C <= 64, 0 <= T <= 32, 1 <= H1, H2 <= 64, ldx >= d + T, d >= 0 (else
+ * GCN_E_BADARG, also for a NULL h, W, scores / dscores, or stats with batch_norm).  fp32 tensors 4-byte
+ * aligned, masks 8-byte, the workspace 16-byte (GCN_E_ALIGN).  Scratch of both calls (short or NULL:
+ * GCN_E_WORKSPACE), with HP = max(H1, H2) rounded up to 16 / 32 / 64, K = C + T, B = min(ceil(n_rows / 64), 2048):
+ *     B * (1 + 3 HP) doubles + B * (K + HP) * HP floats + (1 + 3 HP + (K + HP) * HP) doubles + 256 floats,
+ * each part rounded up to 16 bytes — independent of n_rows above 2048 tiles; 0 outside the rule.  Block b sweeps
+ * the rows [b * R, min((b + 1) * R, n_rows)), R = 64 * ceil(n_rows / (64 * B)), in tiles of 64, a wave per tile.
+ * (ABI 26, additive.)
+ */
+size_t gcn_vmlp_workspace_bytes(int64_t n_rows, int64_t C, int64_t T, int64_t H1, int64_t H2);
+int gcn_vmlp_forward(const float *h, const float *x, int64_t ldx, int64_t d, int64_t n_rows, int64_t C, int64_t T,
+                     const float *W1, const float *b1, int64_t H1, const float *W2, const float *b2, int64_t H2,
+                     const float *W3, const float *b3, int batch_norm, float *stats, float *scores, int64_t *mask1,
+                     int64_t *mask2, void *workspace, size_t workspace_bytes, void *stream);
+int gcn_vmlp_backward(const float *h, const float *x, int64_t ldx, int64_t d, int64_t n_rows, int64_t C, int64_t T,
+                      const float *W1, const float *b1, int64_t H1, const float *W2, const float *b2, int64_t H2,
+                      const float *W3, const float *b3, int batch_norm, const float *stats, const float *dscores,
+                      float *dh, float *gW1, float *gb1, float *gW2, float *gb2, float *gW3, float *gb3,
+                      void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,10 @@ SIGNATURES = {
     "gcn_eval_workspace_bytes": (sz, [i64, i64, i64, i64]),
     "gcn_eval_ingest": (i, [p, p, i64, i64, i64, i64, p, p, p, p, p, sz, p]),
     "gcn_eval_ingest_backward": (i, [p, p, p, p, p, i64, i64, i64, i64, p, p, p]),
+    "gcn_vmlp_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
+    "gcn_vmlp_forward": (i, [p, p, i64, i64, i64, i64, i64, p, p, i64, p, p, i64, p, p, i, p, p, p, p, p, sz, p]),
+    "gcn_vmlp_backward": (i, [p, p, i64, i64, i64, i64, i64, p, p, i64, p, p, i64, p, p, i, p, p,
+                              p, p, p, p, p, p, p, p, sz, p]),
 }
 EXPORTS = tuple(SIGNATURES)
 

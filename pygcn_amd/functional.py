@@ -26,6 +26,10 @@ from pygcn_amd.select import sample_without_replacement, selection_log_prob, top
 # the input side of its evaluator GCN_OVER_MLP (pygcn/models.py:341-355) — the GCN's columns side by side, the
 # flag as the pool's mask, the untouched columns' masked sums, the flag's count — in one sweep: pygcn_amd/evaluator.py
 from pygcn_amd.evaluator import evaluator_ingest  # noqa: E402,F401
+# the score head of its Generator and Hierarchical_Generator (pygcn/models.py:368-370, :391-393) — three Linear
+# layers with ReLU (+ BatchNorm) on cat(h, x[:, d:]) — as fused sweeps that recompute instead of storing:
+# pygcn_amd/head.py
+from pygcn_amd.head import vertex_mlp  # noqa: E402,F401
 
 
 class NLLGrad(torch.Tensor):

@@ -17,6 +17,7 @@ else:
     from pygcn_amd.layers import GraphConvolution
 from pygcn_amd.attention import vertex_attention, vertex_mean  # noqa: E402
 from pygcn_amd.evaluator import evaluator_ingest  # noqa: E402
+from pygcn_amd.head import vertex_mlp  # noqa: E402
 from pygcn_amd.norm import relu_batch_norm  # noqa: E402
 from pygcn_amd.pool import masked_mean_pool  # noqa: E402
 from pygcn_amd.select import sample_without_replacement, selection_log_prob, topk_flag  # noqa: E402
@@ -303,15 +304,19 @@ class Generator(nn.Module):
     synchronisation.  The fork's `print` of four `.item()` values of the scores (:371) — four host
     synchronisations per call — is dropped.  Submodule and parameter names are the fork's
     (GCNLayer.gc1..gc3, MLPLayers.linear1..linear3), so its checkpoints load; `linear_nin` must be
-    nclass + (columns of x past dim_touched)."""
+    nclass + (columns of x past dim_touched).
+
+    `fused_head=True` (opt-in): the MLP runs as `functional.vertex_mlp` — fused HIP sweeps that read the tail of
+    x in place and recompute the hidden activations (pygcn_amd/head.py); same parameters, same state_dict."""
 
     def __init__(self, nfeat, nhid, nclass, dropout, NN, linear_nin, linear_nhid1, linear_nhid2, dim_touched=None,
-                 linear_nout=1, linear_bias=True):
+                 linear_nout=1, linear_bias=True, fused_head=False):
         super(Generator, self).__init__()
         self.GCNLayer = GCNStack(nfeat, nhid, nclass, dropout, nlayers=3)
         self.MLPLayers = GeneratorMLPLayers(linear_nin, linear_nhid1, linear_nhid2, linear_nout, bias=linear_bias)
         self.dim_touched = dim_touched
         self.NN = NN
+        self.fused_head = bool(fused_head)
 
     def scores(self, x, adj):
         """The per-vertex score [N, 1] the flag is taken from (the fork's `mlp_output`)."""
@@ -320,6 +325,8 @@ class Generator(nn.Module):
                                "BatchNorm statistics run over all vertices, and cross-rank reductions are not built")
         d = x.shape[1] if self.dim_touched is None else self.dim_touched
         h = self.GCNLayer(x[:, :d].contiguous(), adj)
+        if self.fused_head:
+            return vertex_mlp(h, x, d, self.MLPLayers, batch_norm=True)
         return self.MLPLayers(torch.cat((h, x[:, d:]), dim=1))
 
     def forward(self, x, adj):
@@ -330,17 +337,19 @@ class Hierarchical_Generator(nn.Module):
     """The fork's Hierarchical_Generator (reference pygcn/models.py:382-408): Generator over the plain
     MLPLayers, where the LAST column of x is a group label that does not enter the MLP (:392) and every
     vertex of `target_group` (0, as the fork hard-codes it, :394) gets the minimum score before the flag
-    is taken (:395-397) — torch ops on [N], the minimum stays on the device."""
+    is taken (:395-397) — torch ops on [N], the minimum stays on the device.  `fused_head=True` as in Generator,
+    without BatchNorm and without the label column."""
 
     target_group = 0
 
     def __init__(self, nfeat, nhid, nclass, dropout, NN, linear_nin, linear_nhid1, linear_nhid2, dim_touched=None,
-                 linear_nout=1, linear_bias=True):
+                 linear_nout=1, linear_bias=True, fused_head=False):
         super(Hierarchical_Generator, self).__init__()
         self.GCNLayer = GCNStack(nfeat, nhid, nclass, dropout, nlayers=3)
         self.MLPLayers = MLPLayers(linear_nin, linear_nhid1, linear_nhid2, linear_nout, bias=linear_bias)
         self.dim_touched = dim_touched
         self.NN = NN
+        self.fused_head = bool(fused_head)
 
     def scores(self, x, adj):
         """The masked per-vertex score [N, 1] the flag is taken from."""
@@ -349,7 +358,10 @@ class Hierarchical_Generator(nn.Module):
                                "runs over all vertices, and cross-rank reductions are not built")
         d = x.shape[1] - 1 if self.dim_touched is None else self.dim_touched
         h = self.GCNLayer(x[:, :d].contiguous(), adj)
-        mlp_output = self.MLPLayers(torch.cat((h, x[:, d:-1]), dim=1))
+        if self.fused_head:
+            mlp_output = vertex_mlp(h, x, d, self.MLPLayers, batch_norm=False, skip_last=1)
+        else:
+            mlp_output = self.MLPLayers(torch.cat((h, x[:, d:-1]), dim=1))
         min_value = (torch.ones_like(mlp_output) * torch.min(mlp_output)).squeeze(1)
         return torch.where(x[:, -1] == self.target_group, min_value, mlp_output.squeeze(1)).unsqueeze(1)
 
@@ -420,8 +432,9 @@ class GCN_OVER_MLP(nn.Module):
 def get_model(config, model_name='GCN'):
     """The fork's `get_model` (reference pygcn/models.py:440-460): `config` is any object with its attribute
     names — gcn_nfeat, gcn_nhid, gcn_nclass, gcn_dropout, NN, dim_touched, linear_nin, linear_nhid1,
-    linear_nhid2, linear_nout, linear_bias.  'MLP', 'GNN_OVER_MLP', 'Generator', 'Hierarchical_Generator' and
-    'SoftGenerator' give the classes of this module.  'GCN', the default, is broken in the fork (it passes six
+    linear_nhid2, linear_nout, linear_bias, and optionally fused_head (the two generators' opt-in).  'MLP',
+    'GNN_OVER_MLP', 'Generator', 'Hierarchical_Generator' and 'SoftGenerator' give the classes of this module.
+    'GCN', the default, is broken in the fork (it passes six
     arguments to a five-argument GCN, :444: a TypeError) and raises TypeError here too; the fork lets an unknown
     name fall through to an unbound local, here it is a ValueError."""
     if model_name == 'GCN':
@@ -441,8 +454,8 @@ def get_model(config, model_name='GCN'):
                             c.linear_bias)
     if model_name == 'Generator':
         return Generator(*gcn, c.linear_nin, c.linear_nhid1, c.linear_nhid2, c.dim_touched, c.linear_nout,
-                         c.linear_bias)
+                         c.linear_bias, getattr(c, 'fused_head', False))
     if model_name == 'Hierarchical_Generator':
         return Hierarchical_Generator(*gcn, c.linear_nin, c.linear_nhid1, c.linear_nhid2, c.dim_touched,
-                                      c.linear_nout, c.linear_bias)
+                                      c.linear_nout, c.linear_bias, getattr(c, 'fused_head', False))
     return SoftGenerator(*gcn, c.linear_nhid1, c.linear_nhid2, c.dim_touched, c.linear_bias)
