@@ -86,7 +86,9 @@ typedef struct gcn_csr_plan {
  * gcn_select_indices / gcn_topk_flag / gcn_race_keys (the end of its Generator, Hierarchical_Generator and of
  * SoftGenerator's policy step, reference pygcn/models.py:373-377, rl-policy-generator.py:324-336).  Also additive to
  * 26: the input side of its evaluator, gcn_eval_workspace_bytes / gcn_eval_ingest / gcn_eval_ingest_backward
- * (GCN_OVER_MLP and PoolLayer, reference pygcn/models.py:333-355, :267-286).
+ * (GCN_OVER_MLP and PoolLayer, reference pygcn/models.py:333-355, :267-286).  Also additive to 26: gcn_dropout_rows /
+ * gcn_csr_take_rows (dropout keyed by a row list and row blocks of a CSR matrix, for the forward pass restricted
+ * to the loss rows' receptive field).
  * 25 (round 4, late): new entry point gcn_gemm_atg256_f32_b3_colsum (the
  * weight gradient with the bias gradient Σ G[rows] as a side result); gcn_gemm_atg256_workspace_bytes grew by
  * 1 KiB per workgroup; struct gcn_gemm_epilogue gained keep_bits_out / mask_bits at its END (zero them);
@@ -832,6 +834,48 @@ int gcn_vmlp_backward(const float *h, const float *x, int64_t ldx, int64_t d, in
                       const float *W3, const float *b3, int batch_norm, const float *stats, const float *dscores,
                       float *dh, float *gW1, float *gb1, float *gW2, float *gb2, float *gW3, float *gb3,
                       void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * What a forward pass RESTRICTED to the receptive field of the loss rows needs beside the products (the model
+ * evaluated on the rows R2 that the loss rows read, pygcn_amd/fused.py): compact tensors whose row r stands for
+ * row rows[r] of the full-height tensor, and the matching row blocks of the adjacency.
+ *
+ *   gcn_dropout_rows   IN PLACE on h [m, F] (dtype fp32 / bf16, row pitch ld >= F elements):
+ *                          h[r, f] = keep(seed, rows[r] + drop_row_base, f) ? h[r, f] * s : 0
+ *                      with keep and s EXACTLY the dropout rule of struct gcn_epilogue above — both forms, eight
+ *                      16-bit fields for T != 32768 and 128 one-bit fields at p = 1/2; counter word 3 = 0, row_lo /
+ *                      row_hi the two words of the 64-bit row, s = 65536 / (65536 - T) — so at equal seed a compact
+ *                      pass draws the mask the full-height launches draw.  rows: DEVICE int64 [m], any order,
+ *                      repeats allowed, any 64-bit value (it only enters the counter; no memory is indexed by it);
+ *                      NULL means rows[r] = r.  seed_dev: optional DEVICE seed, read when the kernel runs (as in
+ *                      struct gcn_epilogue); NULL uses `seed`.  A dropped element becomes +0; a kept bf16 element is
+ *                      multiplied in fp32 and rounded once (nearest-even).  Any F >= 1 and any pitch: runs of four
+ *                      elements travel as one vector access where h is aligned to four elements and ld a multiple of
+ *                      four, else element by element.  Nothing outside the m x F window is written.  One Philox call
+ *                      serves all the columns it covers (8, or 128 at p = 1/2); no atomics, nothing read by the
+ *                      host.  dropout_p = 0 or m = 0 launch nothing.  dropout_p outside [0, 1), m < 0, F < 1 or
+ *                      ld < F is GCN_E_BADARG.
+ *   gcn_csr_take_rows  rows of a CSR matrix as a CSR matrix: output row r receives the stored entries of input row
+ *                      rows[r], in their stored order.  rows: DEVICE int64 [m], each in [0, n_rows) — the CALLER'S
+ *                      duty, it is not checked — in any order, repeats allowed.  rowptr_out [m + 1] (int32, or
+ *                      int64 with out_is64) is SUPPLIED by the caller: the exclusive scan of the selected rows'
+ *                      lengths; col_out / val_out have rowptr_out[m] entries (the count stays on the device: a
+ *                      fixed grid strides over it).  col_map (DEVICE int32 [n_cols], or NULL = columns unchanged)
+ *                      renumbers the columns c -> col_map[c]; an entry with col_map[c] < 0 is written as column 0
+ *                      with value 0 and adds 1 to the DEVICE int32 *n_unmapped (zeroed by the caller; may be NULL) —
+ *                      a guard for a map that is meant to cover every column of the selected rows: the result then
+ *                      stays a valid matrix with a zero entry, and the caller reads the count once.  One thread per
+ *                      output entry, its row found by binary search in rowptr_out: consecutive threads store
+ *                      consecutive entries; no float atomics, two runs give the same bytes.  An output slot that
+ *                      rowptr_out places past the end of its input row is written as (0, 0).  m < 0 is
+ *                      GCN_E_BADARG; m = 0 launches nothing.
+ * (ABI 26, additive.)
+ */
+int gcn_dropout_rows(int dtype, void *h, int64_t ld, const int64_t *rows, int64_t m, int64_t F, float dropout_p,
+                     uint64_t seed, const uint64_t *seed_dev, int64_t drop_row_base, void *stream);
+int gcn_csr_take_rows(const void *rowptr, int rowptr_is64, const int32_t *col, const float *val, const int64_t *rows,
+                      int64_t m, const int32_t *col_map, const void *rowptr_out, int out_is64, int32_t *col_out,
+                      float *val_out, int32_t *n_unmapped, void *stream);
 
 #ifdef __cplusplus
 }

@@ -137,6 +137,8 @@ SIGNATURES = {
     "gcn_vmlp_forward": (i, [p, p, i64, i64, i64, i64, i64, p, p, i64, p, p, i64, p, p, i, p, p, p, p, p, sz, p]),
     "gcn_vmlp_backward": (i, [p, p, i64, i64, i64, i64, i64, p, p, i64, p, p, i64, p, p, i, p, p,
                               p, p, p, p, p, p, p, p, sz, p]),
+    "gcn_dropout_rows": (i, [i, p, i64, p, i64, i64, f32, ctypes.c_uint64, p, i64, p]),
+    "gcn_csr_take_rows": (i, [p, i, p, p, p, i64, p, p, i, p, p, p, p]),
 }
 EXPORTS = tuple(SIGNATURES)
 

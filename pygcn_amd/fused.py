@@ -30,7 +30,10 @@ Only structurally-zero rows are skipped: the result is the same sum of the same 
 
 The forward pass is the ordinary one (both products over all rows, fused bias / ReLU / dropout /
 log_softmax epilogues): the full log-probability matrix exists and can be kept (`keep_full=True`)
-for validation on other rows, as upstream's --fastmode does.
+for validation on other rows, as upstream's --fastmode does.  Opt-in, `restrict_forward=True`
+(GCN2RestrictedFunction): the forward pass too runs on the receptive field of the loss rows — layer 2
+on R, layer 1 on R2, compact activations, the dropout mask of the full pass (spmm.dropout_rows) — and
+the full matrix never exists.
 
 The backward pass is written ONCE, as two stages every route drives — `_loss_rows_stage` (grad_pre2
 and grad_b2) and `_hidden_layer_stage` (grad_W2, grad_pre1, grad_b1, grad_W1 from the saved Â·X) —
@@ -102,6 +105,28 @@ class RowSets:
         mask2 = torch.zeros(graph.shape[1], dtype=torch.bool, device=dev)
         mask2[self.rows2] = True
         self.hint2 = pack_row_flags(mask2)
+
+    _restricted = None       # (graph.val version, a_rows2, a_block), built by restricted()
+    _input_product = None    # (weakref of X, its version, graph.val version, a_rows2·X): restricted_input_product
+
+    def restricted(self, graph):
+        """The two row blocks of Â the RESTRICTED forward pass multiplies with (GCN2RestrictedFunction),
+        cut on the device by CSRGraph.take_rows on first use and again when graph.val was edited in
+        place — the routes that do not restrict the forward pass never pay for them:
+            a_rows2 = Â[R2, :]     [n2, N], global columns: layer 1 on the rows layer 2 reads
+            a_block = Â[R, R2]     [n_u, n2], columns numbered by position in R2: layer 2 on the loss rows
+        (every column of a row of R lies in R2 — that is R2's definition — so no entry is unmapped)."""
+        hit = self._restricted
+        if hit is None or hit[0] != graph.val._version:
+            a_rows2 = graph.take_rows(self.rows2)
+            pos = torch.full((graph.shape[1],), -1, dtype=torch.int32, device=graph.device)
+            pos[self.rows2] = torch.arange(self.n2, dtype=torch.int32, device=graph.device)
+            a_block = graph.take_rows(self.rows_u, col_map=pos, n_cols=self.n2)
+            if a_block.n_unmapped:
+                raise RuntimeError(f"row sets: {a_block.n_unmapped} entries of the loss rows fall outside R2 "
+                                   "(the graph's structure changed since the row sets were built)")
+            hit = self._restricted = (graph.val._version, a_rows2, a_block)
+        return hit[1], hit[2]
 
 
 _ROWSETS = weakref.WeakKeyDictionary()    # graph -> {index-tensor identity: (RowSets, rows)}
@@ -500,6 +525,137 @@ class GCN2Function(torch.autograd.Function):
                 grad = grad.dense()
             grads = _gcn2_backward_dense(ctx, x, w1, w2, h1, logp, grad, needs)
         return (*grads, None, None, None)
+
+
+def restricted_input_product(rs, graph, a_rows2, x):
+    """z_c = Â[R2, :]·X, the compact layer-1 input of the restricted pass — from the row sets' cache
+    under input_product's rules: set_input_product_cache(True), X needs no gradient, and neither X nor
+    the graph's values changed since it was computed."""
+    if not _CACHE_INPUT_PRODUCT or x.requires_grad:
+        return spmm_csr(a_rows2, x)
+    hit = rs._input_product
+    if (hit is not None and hit[0]() is x and hit[1] == x._version and hit[2] == graph.val._version):
+        return hit[3]
+    z = spmm_csr(a_rows2, x)
+    rs._input_product = (weakref.ref(x), x._version, graph.val._version, z)
+    return z
+
+
+def _gcn2_forward_restricted(ctx, x, w1, b1, w2, b2, graph, rs, dropout_p, seed):
+    """Forward pass on the receptive field of the loss rows only: (tensor saved in place of x, h1_c
+    [n2, H], logp_u [n_u, C] in the order of rs.rows_u).  The sums are those of _gcn2_forward for the
+    rows it keeps — layer 2 on the rows R reads h1 on R2, layer 1 on R2 reads X everywhere:
+
+        reassociated layer 1     z_c = Â[R2,:]·X      h1_c = relu(z_c·W1 + b1)        GEMM on n2 rows
+        other widths             sup1 = X·W1 [N, H]   h1_c = relu(Â[R2,:]·sup1 + b1)
+        dropout_rows(h1_c, R2)   the keep bits of the full pass at rows R2 (in place)
+        sup2_c = h1_c·W2         logp_u = log_softmax(Â[R,R2]·sup2_c + b2)
+
+    Fills the ctx fields _hidden_layer_stage reads, as _gcn2_forward does."""
+    a_rows2, a_block = rs.restricted(graph)
+    ctx.graph = graph
+    ctx.scale = _spmm.dropout_scale(dropout_p)
+    bounded = x.dtype == torch.float32 and _gemm.gemm_needs_bounds()
+    ctx.x_bound = _gemm.absmax_cached(x) if bounded else None
+    ctx.reassoc = bool(_gemm.layer_gemm_reassociable(x, w1, b1))
+    ctx.keep_bits = None         # (the mask is h1_c > 0: dropout is not in the GEMM's store here)
+    ctx.z_bound = None
+    h1 = h_bound = z = None
+    if ctx.reassoc:
+        z = restricted_input_product(rs, graph, a_rows2, x)
+        if bounded:
+            ctx.z_bound = a_rows2.inf_norm() * ctx.x_bound * 1.0001
+            h_bound = torch.zeros(1, dtype=torch.float32, device=x.device)       # max|relu(..)|, exact
+        h1 = _gemm.layer_gemm(z, w1, ctx.z_bound, h_bound, bias=b1, relu=True)
+        if h1 is None:                     # (alignment the kernel cannot take)
+            ctx.reassoc, z, h_bound = False, None, None
+        elif bounded:
+            h_bound = h_bound * (1.0001 * ctx.scale)
+    if h1 is None:
+        s_max = torch.zeros(1, dtype=torch.float32, device=x.device) if bounded else None
+        sup1 = _dense_forward(x, w1, ctx.x_bound, s_max)
+        h1 = spmm_csr(a_rows2, sup1, bias=b1, relu=True)
+        del sup1
+        if bounded:
+            h_bound = a_rows2.inf_norm() * s_max
+            if b1 is not None:
+                h_bound = h_bound + b1.detach().abs().max().float()
+            h_bound = h_bound * (1.0001 * ctx.scale)
+    if dropout_p > 0.0:
+        _spmm.dropout_rows(h1, rs.rows2, dropout_p, seed)
+    ctx.h_bound = h_bound
+    logp_u = spmm_csr(a_block, _dense_forward(h1, w2, h_bound), bias=b2, log_softmax=True)
+    ctx.has_bias = (b1 is not None, b2 is not None)
+    ctx.bias_dtypes = (b1.dtype if b1 is not None else None, b2.dtype if b2 is not None else None)
+    return (z if ctx.reassoc else x), h1, logp_u
+
+
+def _gcn2_backward_restricted(ctx, x, w1, w2, h1, out_rows, rs, grad_rows, needs):
+    """Backward pass of the restricted forward: the stages of _gcn2_backward_rows with the hidden layer
+    on the COMPACT h1_c / z_c — "all rows, in order" of their own height n2, so the contiguous kernels
+    run — and layer 1's transpose product on Â[R2,:]ᵀ.  `x` is z_c when layer 1 was reassociated.
+    Returns (grad_x, grad_w1, grad_b1, grad_w2, grad_b2)."""
+    need_x, need_w1, need_b1, need_w2, need_b2 = needs
+    dev, f32 = h1.device, h1.dtype == torch.float32
+    gp, colsum = _loss_rows_stage(grad_rows, out_rows, ctx.has_bias[1] and need_b2, rs)
+    grad_b2 = colsum.to(ctx.bias_dtypes[1]) if colsum is not None else None
+    grad_w1 = grad_w2 = grad_b1 = grad_x = None
+    if not (need_x or need_w1 or need_b1 or need_w2):
+        return grad_x, grad_w1, grad_b1, grad_w2, grad_b2
+    gs_max = torch.zeros(1, dtype=torch.float32, device=dev) if f32 else None
+    grad_sup2 = spmm_csr(rs.at_block, gp.contiguous(), tag="bwd_l2", c_absmax=gs_max)
+    gs_bound = gs_max * 1.0001 if f32 else None
+    gpre1, gpre_bound, grad_w2, grad_b1, grad_w1 = _hidden_layer_stage(
+        h1, w2, grad_sup2, gs_bound, x if ctx.reassoc else None, need_w2, need_w1,
+        ctx.bias_dtypes[0] if (ctx.has_bias[0] and need_b1) else None,
+        ctx.scale, ctx.h_bound, ctx.z_bound, None, rows=rs if rs.n2 == 0 else None)
+    del grad_sup2
+    if (need_x or (need_w1 and not ctx.reassoc)) and rs.n2:
+        a_rows2_t = rs.restricted(ctx.graph)[0].t()
+        if ctx.reassoc:                                     # grad_X = Â[R2,:]ᵀ·(grad_pre1·W1ᵀ)
+            gz = _dense_forward(gpre1, w1.t().contiguous(), gpre_bound)
+            grad_x = spmm_csr(a_rows2_t, gz, tag="bwd_l1")
+        else:
+            grad_sup1 = spmm_csr(a_rows2_t, gpre1.contiguous(), tag="bwd_l1")
+            if need_w1:
+                grad_w1 = _weight_grad(x, grad_sup1)
+            if need_x:
+                grad_x = _dense_forward(grad_sup1, w1.t().contiguous())
+    elif not rs.n2:                                         # (no vertex feeds the loss rows: every sum is empty)
+        if need_x:
+            grad_x = torch.zeros((ctx.graph.shape[1], w1.shape[0]), dtype=h1.dtype, device=dev)
+        if need_w1 and grad_w1 is None:
+            grad_w1 = torch.zeros_like(w1)
+    return grad_x, grad_w1, grad_b1, grad_w2, grad_b2
+
+
+class GCN2RestrictedFunction(torch.autograd.Function):
+    """GCN2RowsFunction's result — log_softmax(Â·dropout(relu(Â·X·W1 + b1))·W2 + b2)[rows] — with the
+    FORWARD pass restricted to the receptive field of `rows` too (opt-in: `model(x, adj, rows=idx,
+    restrict_forward=True)`): layer 2 runs on the rows R alone, layer 1 on R2 = the rows layer 2 reads,
+    and every activation is compact.  The same sums as the full pass for the rows it keeps, the same
+    dropout mask at the same seed (dropout_rows); the full log-probability matrix never exists."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, graph, rows, dropout_p, seed):
+        rs = ctx.rs = row_sets(graph, rows)
+        saved_x, h1, logp_u = _gcn2_forward_restricted(ctx, x, w1, b1, w2, b2, graph, rs, dropout_p, seed)
+        out_rows = logp_u if rs.sorted_unique else logp_u.index_select(0, rs.inverse)
+        ctx.save_for_backward(saved_x, w1, w2, h1, out_rows)
+        return out_rows
+
+    @staticmethod
+    def backward(ctx, grad_rows):
+        x, w1, w2, h1, out_rows = ctx.saved_tensors          # (x is z_c = Â[R2,:]·X on the reassociated path)
+        grads = _gcn2_backward_restricted(ctx, x, w1, w2, h1, out_rows, ctx.rs, grad_rows,
+                                          ctx.needs_input_grad[:5])
+        return (*grads, None, None, None, None)
+
+
+def gcn2_rows_restricted(x, gc1, gc2, graph, rows, dropout_p, seed):
+    """output[rows] of the 2-layer model with forward AND backward pass on the rows' receptive field."""
+    return GCN2RestrictedFunction.apply(x, gc1.weight, gc1.bias, gc2.weight, gc2.bias, graph, rows,
+                                        float(dropout_p), seed)
 
 
 def gcn2_rows(x, gc1, gc2, graph, rows, dropout_p, seed, keep_full=False):

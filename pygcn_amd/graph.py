@@ -305,6 +305,51 @@ class CSRGraph:
             self._t, self._t_val_version = g, self.val._version
         return self._t
 
+    def take_rows(self, rows, col_map=None, n_cols=None):
+        """The rows `rows` of this matrix as a CSRGraph of their own, with its own schedule: row r of the
+        result holds the stored entries of row rows[r], in their stored order (scipy's `A[rows]`).
+        `rows`: int64 indices in any order, repeats allowed.  With `col_map` (int32 device tensor
+        [self.shape[1]]) the columns are renumbered c -> col_map[c] and the result has `n_cols` columns
+        (`A[rows][:, cols]` when col_map holds the position of every column in `cols`); an entry whose
+        column maps to a negative number becomes a zero entry in column 0 and is counted in the result's
+        `n_unmapped` (0 when the map covers the selected rows).  The entries are cut on the device
+        (`gcn_csr_take_rows`); one-off host reads: the range check of `rows`, the entry count, the
+        unmapped count, and the new schedule's sizes."""
+        dev = self.device
+        rows = torch.as_tensor(rows).to(device=dev, dtype=torch.int64).contiguous()
+        if rows.dim() != 1:
+            raise RuntimeError("take_rows: rows must be a 1-D index list")
+        m = int(rows.numel())
+        if m and (int(rows.min()) < 0 or int(rows.max()) >= self.shape[0]):
+            raise RuntimeError("take_rows: row index out of range")
+        if col_map is not None:
+            if n_cols is None:
+                raise RuntimeError("take_rows: col_map needs n_cols")
+            if (col_map.dtype != torch.int32 or col_map.device != dev or col_map.numel() != self.shape[1]
+                    or not col_map.is_contiguous()):
+                raise RuntimeError("take_rows: col_map must be a contiguous int32 device tensor [n_cols of the matrix]")
+            if self.nnz and int(col_map.max()) >= int(n_cols):
+                raise RuntimeError("take_rows: col_map points past n_cols")
+        n_cols = self.shape[1] if col_map is None else int(n_cols)
+        rp = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+        if m:
+            rp[1:] = torch.cumsum((self.rowptr[rows + 1] - self.rowptr[rows]).to(torch.int64), 0)
+        total = int(rp[-1])
+        if total < 2 ** 31 - 1:
+            rp = rp.to(torch.int32)
+        col_out = torch.empty(total, dtype=torch.int32, device=dev)
+        val_out = torch.empty(total, dtype=torch.float32, device=dev)
+        unmapped = torch.zeros(1, dtype=torch.int32, device=dev)
+        if total:
+            _native.launch("gcn_csr_take_rows", dev, self.rowptr.data_ptr(), int(self.rowptr.dtype == torch.int64),
+                           self.col.data_ptr(), self.val.data_ptr(), rows.data_ptr(), m,
+                           col_map.data_ptr() if col_map is not None else None, rp.data_ptr(),
+                           int(rp.dtype == torch.int64), col_out.data_ptr(), val_out.data_ptr(), unmapped.data_ptr())
+        g = CSRGraph(rp, col_out, val_out, (m, n_cols), item_cost=self.item_cost, long_thresh=self.long_thresh,
+                     validate=False)
+        g.n_unmapped = int(unmapped) if (col_map is not None and total) else 0
+        return g
+
     def row_normalize_(self):
         """In place D^-1 · A on the device (`gcn_row_normalize_device`): the reference's
         `normalize(mx)` (pygcn/utils.py:390-397); rows whose sum has an infinite float32

@@ -32,7 +32,7 @@ class GCN(nn.Module):
         self.gc2 = GraphConvolution(nhid, nclass)
         self.dropout = dropout
 
-    def forward(self, x, adj, rows=None, keep_full=False):
+    def forward(self, x, adj, rows=None, keep_full=False, restrict_forward=False):
         """`model(x, adj)`: the reference call — log-probabilities of every vertex.
 
         `model(x, adj, rows=idx)` (extension): the same forward pass, returning `output[idx]` —
@@ -41,7 +41,16 @@ class GCN(nn.Module):
         pass run on the rows that can be non-zero (pygcn_amd/fused.py): same gradients, no
         [N, ·]-sized zero fills, scatters or sweeps, no host synchronisation.  With
         `keep_full=True` the result is `(output[idx], output.detach())` — the full matrix for
-        validation on other rows, as upstream's --fastmode uses it."""
+        validation on other rows, as upstream's --fastmode uses it.
+
+        `model(x, adj, rows=idx, restrict_forward=True)` (opt-in): the FORWARD pass too runs on the
+        receptive field of `idx` only — layer 2 on the rows idx, layer 1 on the rows those read — with
+        the same result and, at the same generator state, the same dropout mask.  It needs a CSRGraph
+        the one-node path covers and cannot keep the full matrix (it never exists); anything else
+        raises, there is no fallback to the full pass.  Works in eval() and under no_grad (validation
+        on idx_val is its own restricted pass)."""
+        if restrict_forward:
+            return self._forward_restricted(x, adj, rows, keep_full)
         if rows is not None:
             return self._forward_rows(x, adj, rows, keep_full)
         # (below ROWGRAD_MIN_ROWS vertices an epoch is launch-bound — Cora: ~1 ms — and the plain
@@ -101,6 +110,27 @@ class GCN(nn.Module):
             return (out, full) if keep_full else out
         full = self.forward(x, adj)          # layer-by-layer path (sharded / dense adjacency / odd shapes)
         return (full[rows], full.detach()) if keep_full else full[rows]
+
+    def _forward_restricted(self, x, adj, rows, keep_full):
+        fused, CSRGraph, _, dropout_seed_for = self._imports()
+        why = None
+        if rows is None:
+            why = "it needs `rows`, the rows the loss (or the validation) reads"
+        elif keep_full:
+            why = "keep_full=True asks for the full log-probability matrix, which a restricted pass never forms"
+        elif isinstance(adj, ShardedGraph):
+            why = "a ShardedGraph adjacency is not supported (the sharded path restricts its backward pass only)"
+        elif not isinstance(adj, CSRGraph):
+            kind = f"a {adj.layout} tensor" if isinstance(adj, torch.Tensor) else type(adj).__name__
+            why = f"the adjacency must be a CSRGraph, got {kind} (dense and COO adjacencies take the full pass)"
+        elif self._one_node_graph(x, adj) is None:
+            why = ("the one-node path does not cover this call (fused.fusable: a square CSRGraph, a 2-D device "
+                   "input of the parameters' dtype, a class count the fused log_softmax takes)")
+        if why is not None:
+            raise RuntimeError(f"GCN.forward(restrict_forward=True): {why}")
+        p = self.dropout if self.training else 0.0
+        seed = dropout_seed_for(x) if p > 0.0 else 0
+        return fused.gcn2_rows_restricted(x, self.gc1, self.gc2, adj, rows, p, seed)
 
 
 class GCNStack(nn.Module):

@@ -417,6 +417,30 @@ def dropout_seed_for(tensor):
     return t
 
 
+def dropout_rows(h, rows, p, seed, row_base=0):
+    """IN PLACE on the compact tensor h [m, F] (fp32 / bf16, unit column stride, any row pitch) whose
+    row r stands for row rows[r] of a full-height tensor: h[r, f] = keep ? h[r, f] · s : 0 with the keep
+    bit and the scale of the fused epilogues at (seed, rows[r] + row_base, f) — C-ABI gcn_dropout_rows.
+    `spmm_csr(g, S, relu=True, dropout_p=p, seed=σ)[rows]` and `dropout_rows(spmm_csr(g, S,
+    relu=True)[rows], rows, p, σ)` are the same bits.  `rows`: int64 device list, any order, repeats
+    allowed, or None = 0 .. m-1; `seed` as in spmm_csr (a 1-element int64 device tensor is read when the
+    kernel runs).  Returns h."""
+    _require_cuda(h, "h")
+    if h.dim() != 2 or h.dtype not in _DTYPES or (h.shape[1] > 0 and h.stride(1) != 1):
+        raise RuntimeError("dropout_rows: h must be a 2-D float32 / bfloat16 tensor with unit column stride")
+    m, F = h.shape
+    if rows is not None:
+        if (rows.dtype != torch.int64 or rows.device != h.device or rows.dim() != 1 or rows.numel() != m
+                or not rows.is_contiguous()):
+            raise RuntimeError("dropout_rows: rows must be a contiguous int64 device list, one entry per row of h")
+    if m == 0 or F == 0:
+        return h
+    seed, seed_dev = _seed_fields(seed, h.device, "dropout_rows")
+    _native.launch("gcn_dropout_rows", h.device, _DTYPES[h.dtype], h.data_ptr(), h.stride(0) if m > 1 else max(h.stride(0), F),
+                   rows.data_ptr() if rows is not None else None, m, F, float(p), seed, seed_dev, int(row_base))
+    return h
+
+
 def check_fused_epilogue(relu, dropout_p, log_softmax=False):
     """The argument rules of the fused epilogues, for every layer function's forward."""
     if dropout_p > 0.0 and not relu:

@@ -35,6 +35,9 @@ VALUE_FLAGS = (
 SWITCHES = (
     ("--no-cuda", "Disables CUDA training (unsupported here: the path is HIP-only)."),
     ("--fastmode", "Validate during training pass."),
+    ("--restrict_forward", "Run the forward pass on the receptive field of the rows it is asked for only "
+                           "(extension, pygcn_amd/fused.py): training on idx_train, validation and test as "
+                           "restricted passes of their own."),
 )
 
 
@@ -64,6 +67,10 @@ class Run:
         self.opt = torch.optim.Adam(self.model.parameters(), lr=args.lr,
                                     weight_decay=args.weight_decay)
         self.fastmode = args.fastmode
+        self.restrict_forward = args.restrict_forward
+        if self.restrict_forward:      # (the restricted pass takes the prepared handle, not the COO tensor)
+            from pygcn_amd.graph import as_graph
+            self.adj = as_graph(self.adj)
 
     def score(self, log_probs, name):
         rows = self.split[name]
@@ -77,6 +84,8 @@ class Run:
         # (train.py:150-153).  Same forward pass; the model is told which rows the loss reads so
         # that the backward pass stays on the rows that can be non-zero (pygcn_amd/fused.py)
         rows = self.split["train"]
+        if self.restrict_forward:
+            return self.restricted_epoch(number, started, rows)
         train_rows, log_probs = self.model(self.features, self.adj, rows=rows, keep_full=True)
         loss, acc = nll_loss(train_rows, self.labels[rows]), accuracy(train_rows, self.labels[rows])
         loss.backward()
@@ -89,9 +98,39 @@ class Run:
               % (number, loss.item(), acc.item(), val_loss.item(), val_acc.item(),
                  time.time() - started))
 
+    def restricted_rows(self, name):
+        """Log-probabilities of the split's rows from a forward pass on their receptive field only."""
+        return self.model(self.features, self.adj, rows=self.split[name], restrict_forward=True)
+
+    def restricted_epoch(self, number, started, rows):
+        """The epoch with --restrict_forward: no pass forms the full matrix, so validation is a restricted
+        pass of its own over idx_val — after the step with dropout off, or, under --fastmode, with the
+        parameters and the mode of the training pass (upstream validates on that pass's output there; with
+        dropout the mask is a fresh draw)."""
+        train_rows = self.restricted_rows("train")
+        loss, acc = nll_loss(train_rows, self.labels[rows]), accuracy(train_rows, self.labels[rows])
+        loss.backward()
+        val_labels = self.labels[self.split["val"]]
+        with torch.no_grad():
+            if self.fastmode:
+                val_rows = self.restricted_rows("val")
+            self.opt.step()
+            if not self.fastmode:
+                self.model.eval()
+                val_rows = self.restricted_rows("val")
+        val_loss, val_acc = nll_loss(val_rows, val_labels), accuracy(val_rows, val_labels)
+        print("Epoch: %04d loss_train: %.4f acc_train: %.4f loss_val: %.4f acc_val: %.4f time: %.4fs"
+              % (number, loss.item(), acc.item(), val_loss.item(), val_acc.item(),
+                 time.time() - started))
+
     def test(self):
         self.model.eval()
-        loss, acc = self.score(self.model(self.features, self.adj), "test")
+        if self.restrict_forward:
+            with torch.no_grad():
+                rows, labels = self.restricted_rows("test"), self.labels[self.split["test"]]
+            loss, acc = nll_loss(rows, labels), accuracy(rows, labels)
+        else:
+            loss, acc = self.score(self.model(self.features, self.adj), "test")
         print("Test set results: loss= %.4f accuracy= %.4f" % (loss.item(), acc.item()))
 
 

@@ -1,0 +1,546 @@
+"""`model(x, adj, rows=idx, restrict_forward=True)` — forward AND backward pass on the receptive field of the
+loss rows (pygcn_amd/fused.py, GCN2RestrictedFunction) — and its two kernels: dropout keyed by a row list
+(`spmm.dropout_rows`, C-ABI gcn_dropout_rows) and row blocks of a CSR matrix cut on the device
+(`CSRGraph.take_rows`, C-ABI gcn_csr_take_rows).  The route is held against the oracle with the checks of
+tests/test_fused_gpu.py and against the `rows=` route at the project's 1e-5 contract."""
+import numpy as np
+import pytest
+import scipy.sparse as sp
+import torch
+
+import inputs as gin
+from conftest import assert_normwise, assert_parity, load_golden
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-5
+ROUTES = 1e-5        # two fp32 evaluations of the same sums (profiles/r04_parity_ledger.md: <= 3.7e-6)
+SEED = 0x9E3779B97F4A7C15
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(autouse=True)
+def poison():
+    """Tensors whose rows are left unwritten on purpose are pre-filled with NaN (tests/test_fused_gpu.py)."""
+    from pygcn_amd import spmm as S
+    S._poison_unwritten = True
+    yield
+    S._poison_unwritten = False
+
+
+# ------------------------------------------------------------------------------------------ dropout_rows
+def _bits(t):
+    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+
+
+def _row_list(m, rng):
+    """Unsorted, with repeats, one entry past 2^33 (the high counter word; no memory is indexed by it)."""
+    rows = rng.integers(0, 5000, m)
+    if m > 2:
+        rows[m // 2] = rows[0]
+    rows = rows.astype(np.int64)
+    rows[m - 1] = 2 ** 33 + 5
+    return rows
+
+
+def _expected_dropout(h_cpu, keep, scale):
+    s = torch.tensor(float(scale), dtype=torch.float32)
+    kept = (h_cpu.float() * s).to(h_cpu.dtype)           # one fp32 product, rounded once to the storage type
+    return torch.where(torch.from_numpy(keep), kept, torch.zeros((), dtype=h_cpu.dtype))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("p", [0.5, 0.3])
+def test_dropout_rows_draws_the_header_mask(oracle, dev, p, dtype):
+    """Every (m, F) of the issue, two pitches each (ld = F + 1: element accesses; the next multiple of 4 above
+    F: vector accesses with an element tail), the padding NaN before and after; bitwise."""
+    from pygcn_amd import spmm as S
+    rng = np.random.default_rng(7)
+    scale = oracle.dropout_scale(p)
+    for m in (1, 63, 64, 65, 1000):
+        rows = _row_list(m, rng)
+        rows_t = torch.from_numpy(rows).to(dev)
+        for F in (1, 7, 16, 100, 256, 512, 520):
+            keep = oracle.dropout_keep(SEED, rows, F, p)
+            for ld in (F + 1, (F // 4 + 1) * 4):
+                h_cpu = torch.from_numpy(gin.dense((m, F), m + F)).to(dtype)
+                buf = torch.full((m, ld), float("nan"), dtype=dtype, device=dev)
+                buf[:, :F] = h_cpu.to(dev)
+                got = S.dropout_rows(buf[:, :F], rows_t, p, SEED)
+                assert got.data_ptr() == buf.data_ptr()
+                want = _expected_dropout(h_cpu, keep, scale)
+                assert torch.equal(_bits(buf[:, :F].cpu()), _bits(want)), (m, F, ld)
+                assert bool(torch.isnan(buf[:, F:]).all()), (m, F, ld, "padding written")
+    # rows = NULL with a row base, and a device-resident seed
+    m, F, base = 65, 520, 2 ** 33 + 123
+    keep = oracle.dropout_keep(SEED, np.arange(m), F, p, row_base=base)
+    h_cpu = torch.from_numpy(gin.dense((m, F), 3)).to(dtype)
+    for seed in (SEED, torch.tensor([SEED - (1 << 64)], dtype=torch.int64, device=dev)):
+        got = S.dropout_rows(h_cpu.to(dev), None, p, seed, row_base=base)
+        assert torch.equal(_bits(got.cpu()), _bits(_expected_dropout(h_cpu, keep, scale)))
+
+
+@pytest.mark.parametrize("p", [0.5, 0.3])
+@pytest.mark.parametrize("F", [256, 48])
+def test_dropout_rows_is_the_fused_epilogue_at_those_rows(dev, p, F):
+    from pygcn_amd import CSRGraph
+    from pygcn_amd import spmm as S
+    from pygcn_amd.utils import rmat_graph
+    n = 5000
+    rowptr, col, val = rmat_graph(n, 40000, seed=5, device="cpu")
+    g = CSRGraph(rowptr.to(dev), col.to(dev), val.to(dev), (n, n))
+    B = torch.from_numpy(gin.dense((n, F), 4)).to(dev)
+    bias = torch.from_numpy(gin.dense((F,), 5)).to(dev)
+    rows = torch.from_numpy(np.random.default_rng(1).integers(0, n, 700)).to(dev)
+    fused = S.spmm_csr(g, B, bias=bias, relu=True, dropout_p=p, seed=SEED)[rows]
+    apart = S.dropout_rows(S.spmm_csr(g, B, bias=bias, relu=True)[rows], rows, p, SEED)
+    assert torch.equal(_bits(fused), _bits(apart))
+    assert 0 < int((fused > 0).sum()) < int((S.spmm_csr(g, B, bias=bias, relu=True)[rows] > 0).sum())
+
+
+# ------------------------------------------------------------------------------------------ take_rows
+def _graph_500():
+    """500 vertices: row 3 empty, row 5 with one entry, row 7 with 300 (above the 64-entry tile and long_thresh)."""
+    n = 500
+    rng = np.random.default_rng(11)
+    A = sp.random(n, n, density=0.02, random_state=12, format="lil", dtype=np.float32)
+    A[3, :] = 0
+    A[5, :] = 0
+    A[5, 17] = 0.5
+    A[7, :] = 0
+    A[7, np.sort(rng.permutation(n)[:300])] = rng.random(300).astype(np.float32) + 0.1
+    A[n - 1, n - 1] = 0.25
+    A = sp.csr_matrix(A, dtype=np.float32)
+    A.eliminate_zeros()
+    A.sort_indices()
+    lens = np.diff(A.indptr)
+    assert lens[3] == 0 and lens[5] == 1 and lens[7] == 300
+    return A
+
+
+ROW_LISTS = {"descending": np.arange(499, -1, -1), "duplicates": np.array([7, 7, 5, 3, 499, 0, 7, 3, 250]),
+             "last": np.array([499]), "empty": np.zeros(0, np.int64)}
+
+
+@pytest.mark.parametrize("rowptr_dtype", [torch.int32, torch.int64], ids=["rp32", "rp64"])
+@pytest.mark.parametrize("which", list(ROW_LISTS))
+def test_take_rows_equals_scipy(dev, which, rowptr_dtype):
+    from pygcn_amd import CSRGraph
+    from pygcn_amd import spmm as S
+    A = _graph_500()
+    n = A.shape[0]
+    g = CSRGraph(torch.from_numpy(A.indptr.astype(np.int64)).to(dev).to(rowptr_dtype),
+                 torch.from_numpy(A.indices.astype(np.int32)).to(dev), torch.from_numpy(A.data).to(dev), (n, n))
+    rows = ROW_LISTS[which].astype(np.int64)
+    rows_t = torch.from_numpy(rows).to(dev)
+    B = torch.from_numpy(gin.dense((n, 64), 2)).to(dev)
+
+    def same(t, want):
+        assert t.shape == want.shape and t.nnz == want.nnz and t.n_unmapped == 0
+        assert np.array_equal(t.rowptr.cpu().numpy().astype(np.int64), want.indptr.astype(np.int64))
+        assert np.array_equal(t.col.cpu().numpy(), want.indices)            # (entry order included)
+        assert np.array_equal(t.val.cpu().numpy(), want.data)
+    # without a map: scipy's row selection keeps the stored order
+    t = g.take_rows(rows_t)
+    same(t, A[rows])
+    if len(rows):       # its own schedule (the 300-entry row is chunked): the product runs on it
+        assert_normwise(S.spmm_csr(t, B).cpu(), A[rows].astype(np.float64) @ B.cpu().numpy().astype(np.float64),
+                        TOL, "product on the taken rows")
+    # with a map: the columns that occur in the selected rows, numbered by position (a monotone map keeps every
+    # row sorted, which is scipy's order after sort_indices)
+    cols = np.unique(A[rows].indices)
+    col_map = np.full(n, -1, np.int32)
+    col_map[cols] = np.arange(len(cols), dtype=np.int32)
+    want = A[rows][:, cols]
+    want.sort_indices()
+    t = g.take_rows(rows_t, col_map=torch.from_numpy(col_map).to(dev), n_cols=len(cols))
+    same(t, want)
+    if len(rows) and which != "last":
+        # the guard: one used column unmapped -> zero-valued entries in column 0, counted; still a valid matrix
+        c0 = int(cols[len(cols) // 2])
+        broken = col_map.copy()
+        broken[c0] = -1
+        t = g.take_rows(rows_t, col_map=torch.from_numpy(broken).to(dev), n_cols=len(cols))
+        assert t.n_unmapped == int((A[rows].indices == c0).sum()) > 0
+        assert t.nnz == want.nnz and int(t.col.min()) >= 0 and int(t.col.max()) < len(cols)
+        zeroed = want.tolil()
+        zeroed[:, col_map[c0]] = 0
+        Bc = B[: len(cols)]
+        assert_normwise(S.spmm_csr(t, Bc).cpu(), sp.csr_matrix(zeroed).astype(np.float64) @ Bc.cpu().numpy().astype(np.float64),
+                        TOL, "product with an unmapped column")
+
+
+# ------------------------------------------------------------------------------------------ the route
+_ORACLE_STEPS = {}
+
+
+def _oracle_step(oracle, key, x, a, p, labels, idx, need_x, relu_mask=None):
+    """The oracle's step and its float64 twin, computed once per case (the GEMM schemes share it)."""
+    if key not in _ORACLE_STEPS:
+        ref_loss, fw, grads, extra = oracle.gcn2_loss_backward(x, a, p, labels, idx, need_grad_x=need_x,
+                                                               relu_mask=relu_mask)
+        _, _, grads64 = oracle.gcn2_loss_backward_f64(x, a, p, labels, idx,
+                                                      relu_mask=fw["h1"] > 0 if relu_mask is None else relu_mask)
+        _ORACLE_STEPS[key] = (ref_loss, fw["logp"][idx], grads, grads64, extra["grad_x"] if need_x else None)
+    return _ORACLE_STEPS[key]
+
+
+def _check(key, model, x, graph, a, labels, idx, oracle, need_x=False, relu_mask=None):
+    """tests/test_fused_gpu.py's `_check` for the restricted route: selected rows, loss, four parameter
+    gradients (float64 arbiter), grad_x.  `relu_mask`: the ReLU derivative handed to the oracle (the device's,
+    tests/_sampling.py device_relu_mask) instead of the oracle's own."""
+    dev = x.device
+    idx_t = torch.from_numpy(np.asarray(idx)).to(dev)
+    model.train()
+    model.zero_grad()
+    out_rows = model(x, graph, rows=idx_t, restrict_forward=True)
+    loss = torch.nn.functional.nll_loss(out_rows, torch.from_numpy(labels).to(dev)[idx_t])
+    loss.backward()
+    p = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
+    ref_loss, ref_rows, grads, grads64, ref_gx = _oracle_step(oracle, key, x.detach().cpu().numpy(), a, p, labels,
+                                                              np.asarray(idx), need_x, relu_mask)
+    assert_normwise(out_rows.detach().cpu(), ref_rows, TOL, "selected rows")
+    assert abs(loss.item() - ref_loss) <= TOL * abs(ref_loss)
+    for k, v in grads.items():
+        mod, name = k.split(".")
+        got = getattr(getattr(model, mod), name).grad
+        assert got is not None and torch.isfinite(got).all(), k
+        assert_parity(got.cpu(), v, grads64[k], k + ".grad")
+    if need_x:
+        assert_normwise(x.grad.cpu(), ref_gx, TOL, "grad_x")
+    return {k: q.grad.detach().clone() for k, q in model.named_parameters()}
+
+
+def _rmat(oracle, dev, n, edges, seed):
+    from pygcn_amd import CSRGraph
+    from pygcn_amd.utils import rmat_graph
+    rowptr, col, val = rmat_graph(n, edges, seed=seed, device="cpu")
+    a = oracle.CSR(rowptr.numpy().astype(np.int64), col.numpy(), val.numpy(), (n, n))
+    return CSRGraph(rowptr.to(dev), col.to(dev), val.to(dev), (n, n)), a
+
+
+def test_cora_step_through_the_restricted_route(oracle, dev, gemm_scheme):
+    """1433 -> 16 -> 7 on the committed Cora graph: the non-reassociated layer 1 (X·W1 over all rows, then
+    Â[R2,:]); also against G2, the step captured from the imported reference layer."""
+    from pygcn_amd import GCN
+    from pygcn_amd.graph import as_graph
+    from pygcn_amd.utils import load_data
+    adj, _, _, idx_train, _, _ = load_data()
+    g = np.load(gin.__file__.replace("inputs.py", "cora_graph.npz"))
+    a = oracle.cora_adjacency(g["edges"], int(g["n"]))
+    x = torch.from_numpy(gin.cora_features()).to(dev)
+    torch.manual_seed(42)
+    model = GCN(1433, 16, 7, dropout=0.0).to(dev)
+    got = _check("cora", model, x, as_graph(adj.to(dev)), a, gin.cora_labels(), idx_train.numpy(), oracle)
+    g2 = load_golden("g2_cora_step.npz")
+    for mod, name in (("gc1", "weight"), ("gc1", "bias"), ("gc2", "weight"), ("gc2", "bias")):
+        assert_normwise(got[f"{mod}.{name}"].cpu(), g2[f"{mod}_{name}_grad"], TOL, f"G2 {mod}_{name}_grad")
+
+
+@pytest.mark.parametrize("fin,hid,ncls,share", [(256, 256, 256, 0.05), (48, 64, 16, 0.3), (256, 256, 64, 0.9)])
+def test_rmat_step_matches_oracle(oracle, dev, gemm_scheme, fin, hid, ncls, share):
+    from pygcn_amd import GCN
+    n = 30000
+    g, a = _rmat(oracle, dev, n, 300000, 21)
+    rng = np.random.default_rng(fin + ncls)
+    x = torch.from_numpy(gin.dense((n, fin), 5)).to(dev)
+    labels = rng.integers(0, ncls, n)
+    idx = rng.permutation(n)[: int(n * share)]            # unsorted on purpose
+    torch.manual_seed(1)
+    model = GCN(fin, hid, ncls, dropout=0.0).to(dev)
+    _check(("rmat", fin, hid, ncls, share), model, x, g, a, labels, idx, oracle)
+
+
+@pytest.mark.parametrize("start,count", [(0, 1500), (29000, 1000)])
+def test_loss_rows_that_are_a_range(oracle, dev, gemm_scheme, start, count):
+    from pygcn_amd import GCN, fused
+    n = 30000
+    g, a = _rmat(oracle, dev, n, 300000, 22)
+    x = torch.from_numpy(gin.dense((n, 256), 6)).to(dev)
+    labels = np.random.default_rng(start).integers(0, 256, n)
+    idx = np.arange(start, start + count)
+    rs = fused.row_sets(g, torch.from_numpy(idx).to(dev))
+    a_rows2, a_block = rs.restricted(g)
+    assert rs.sorted_unique and a_rows2.shape == (rs.n2, n) and a_block.shape == (count, rs.n2)
+    assert a_block.nnz == rs.at_block.nnz and a_block.n_unmapped == 0
+    torch.manual_seed(2)
+    model = GCN(256, 256, 256, dropout=0.0).to(dev)
+    _check(("range", start, count), model, x, g, a, labels, idx, oracle)
+
+
+def test_duplicate_unsorted_rows_and_the_input_gradient(oracle, dev, gemm_scheme):
+    from pygcn_amd import GCN
+    n, F = 20000, 64
+    g, a = _rmat(oracle, dev, n, 150000, 22)
+    rng = np.random.default_rng(3)
+    labels = rng.integers(0, F, n)
+    idx = np.concatenate([rng.integers(0, n, 900), [7, 7, 7, n - 1]])
+    torch.manual_seed(2)
+    model = GCN(F, F, F, dropout=0.0).to(dev)
+    x = torch.from_numpy(gin.dense((n, F), 6)).to(dev).requires_grad_(True)
+    _check("duplicates", model, x, g, a, labels, idx, oracle, need_x=True)
+
+
+def test_input_gradient_of_the_reassociated_layer(oracle, dev, gemm_scheme):
+    """256 -> 256: grad_X = Â[R2,:]ᵀ·(grad_pre1·W1ᵀ), the transpose of the row block.  1000 loss rows: one hidden
+    unit within rounding of zero that sits on the other side of the ReLU in the oracle's summation order moves
+    grad_W1 by 1e-2 of its norm (measured), so the oracle is given the device's ReLU derivative — after
+    device_relu_mask has asserted that the two differ only within 1e-5 of zero."""
+    from _sampling import device_relu_mask
+    from pygcn_amd import GCN
+    n, F = 20000, 256
+    g, a = _rmat(oracle, dev, n, 150000, 23)
+    rng = np.random.default_rng(4)
+    labels = rng.integers(0, F, n)
+    idx = rng.permutation(n)[:1000]
+    torch.manual_seed(3)
+    model = GCN(F, F, F, dropout=0.0).to(dev)
+    x = torch.from_numpy(gin.dense((n, F), 7)).to(dev).requires_grad_(True)
+    mask, flips = device_relu_mask(oracle, model, x.detach(), g, a)
+    print(f"hidden units on the other side of the ReLU than in the oracle: {flips}")
+    _check(("grad_x 256", gemm_scheme), model, x, g, a, labels, idx, oracle, need_x=True, relu_mask=mask)
+
+
+def test_bf16_restricted_route(oracle, dev):
+    """bf16 128 -> 128 -> 128 at the gates of tests/test_fused_gpu.py::test_bf16_one_node_path."""
+    from pygcn_amd import GCN
+    n, F = 20000, 128
+    g, a = _rmat(oracle, dev, n, 200000, 3)
+    x16 = torch.from_numpy(gin.dense((n, F), 1)).to(torch.bfloat16)
+    y = np.random.default_rng(2).integers(0, F, n)
+    idx = np.arange(n // 10)
+    torch.manual_seed(5)
+    m16 = GCN(F, F, F, dropout=0.0).to(torch.bfloat16).to(dev)
+    idx_t = torch.from_numpy(idx).to(dev)
+    out = m16(x16.to(dev), g, rows=idx_t, restrict_forward=True)
+    assert out.dtype == torch.bfloat16 and out.shape == (len(idx), F)
+    loss = torch.nn.functional.nll_loss(out.float(), torch.from_numpy(y).to(dev)[idx_t])
+    loss.backward()
+    p = {k: v.detach().float().cpu().numpy() for k, v in m16.state_dict().items()}
+    ref_loss, fw, grads, _ = oracle.gcn2_loss_backward(x16.float().numpy(), a, p, y, idx)
+    assert_normwise(out.float().detach().cpu(), fw["logp"][idx], 2.0 ** -6, "logp rows")
+    assert abs(loss.item() - ref_loss) <= 2.0 ** -6 * abs(ref_loss)
+    for k, v in grads.items():
+        mod, name = k.split(".")
+        assert_normwise(getattr(getattr(m16, mod), name).grad.float().cpu(), v, 2.0 ** -4, k + ".grad")
+
+
+@pytest.mark.parametrize("fin,hid,ncls", [(256, 256, 256), (48, 64, 16)])
+@pytest.mark.parametrize("p", [0.0, 0.4, 0.5])
+def test_restricted_route_equals_the_rows_route(dev, gemm_scheme, p, fin, hid, ncls):
+    """Same torch.manual_seed, same mask: output rows and all four gradients of the two routes agree at the
+    1e-5 contract in training mode (a mask keyed on the compact row numbers would be an O(1) difference) and in
+    eval(), where no_grad validation runs."""
+    from pygcn_amd import GCN, CSRGraph
+    from pygcn_amd.utils import rmat_graph
+    n = 30000
+    rowptr, col, val = rmat_graph(n, 300000, seed=24, device=dev)
+    g = CSRGraph(rowptr, col, val, (n, n))
+    x = torch.from_numpy(gin.dense((n, fin), 8)).to(dev)
+    labels = torch.from_numpy(np.random.default_rng(5).integers(0, ncls, n)).to(dev)
+    idx = torch.from_numpy(np.random.default_rng(6).permutation(n)[: n // 15]).to(dev)      # unsorted
+    torch.manual_seed(7)
+    model = GCN(fin, hid, ncls, dropout=p).to(dev)
+    model.train()
+    results = []
+    for restrict in (False, True):
+        model.zero_grad(set_to_none=True)
+        torch.manual_seed(11)
+        out = model(x, g, rows=idx, restrict_forward=restrict)
+        torch.nn.functional.nll_loss(out, labels[idx]).backward()
+        results.append((out.detach().clone(), {k: q.grad.clone() for k, q in model.named_parameters()}))
+    assert_normwise(results[1][0].cpu(), results[0][0].cpu().numpy(), ROUTES, "training rows")
+    for k, q in results[0][1].items():
+        assert_normwise(results[1][1][k].cpu(), q.cpu().numpy(), ROUTES, "restricted vs rows=: " + k)
+    if p > 0.0:         # the mask is there at all: the rows differ from the dropout-free rows
+        model.eval()
+        with torch.no_grad():
+            plain = model(x, g, rows=idx)
+        assert float((plain - results[0][0]).abs().max()) > 1e-3 * float(plain.abs().max())
+    model.eval()
+    with torch.no_grad():
+        a, b = model(x, g, rows=idx), model(x, g, rows=idx, restrict_forward=True)
+    assert not b.requires_grad
+    assert_normwise(b.cpu(), a.cpu().numpy(), ROUTES, "eval rows")
+
+
+def test_input_product_cache_is_bitwise_neutral_and_notices_changes(dev):
+    """set_input_product_cache(True): the compact z_c = Â[R2,:]·X is computed once per (graph, rows, X, versions);
+    the results are the uncached bits; an in-place edit of X or of graph.val is noticed."""
+    from pygcn_amd import GCN, CSRGraph, fused
+    from pygcn_amd import spmm as S
+    from pygcn_amd.utils import rmat_graph
+    n, F_ = 20000, 256
+    rowptr, col, val = rmat_graph(n, 200000, seed=81, device=dev)
+    g = CSRGraph(rowptr, col, val, (n, n))
+    x = torch.randn(n, F_, device=dev)
+    labels = torch.randint(0, F_, (n,), device=dev)
+    idx = torch.arange(n // 10, device=dev)
+    torch.manual_seed(8)
+    model = GCN(F_, F_, F_, dropout=0.0).to(dev)
+    model.train()
+
+    def step():
+        model.zero_grad(set_to_none=True)
+        out = model(x, g, rows=idx, restrict_forward=True)
+        torch.nn.functional.nll_loss(out, labels[idx]).backward()
+        return out.detach().clone(), [p.grad.clone() for p in model.parameters()]
+    base = step()
+    launches = []
+    S.set_timing_records(launches)
+    try:
+        fused.set_input_product_cache(True)
+        first, second = step(), step()
+        n_fwd = [sum(1 for r in launches if r[0] == "fwd")]
+        x.mul_(1.0)                                           # version bump: must recompute
+        third = step()
+        n_fwd.append(sum(1 for r in launches if r[0] == "fwd"))
+        g.val.mul_(0.5)                                       # the adjacency's values: new blocks, new product
+        model.eval()
+        with torch.no_grad():
+            halved = model(x, g, rows=idx, restrict_forward=True)
+            n_fwd.append(sum(1 for r in launches if r[0] == "fwd"))
+            fused.set_input_product_cache(False)
+            want = model(x, g, rows=idx)
+    finally:
+        fused.set_input_product_cache(False)
+        S.set_timing_records(None)
+    for got in (first, second, third):
+        assert torch.equal(got[0], base[0])
+        for a, b in zip(got[1], base[1]):
+            assert torch.equal(a, b)
+    # 2 forward products (Â[R2,:]·X and layer 2's block), then 1 (cached), then 2 again, and 2 after the edit
+    assert n_fwd[0] == 2 + 1 and n_fwd[1] == n_fwd[0] + 2 and n_fwd[2] == n_fwd[1] + 2
+    assert_normwise(halved.cpu(), want.cpu().numpy(), ROUTES, "after graph.val changed")
+    assert float((halved - base[0]).abs().max()) > 1e-3 * float(base[0].abs().max())
+
+
+def test_second_restricted_step_has_no_host_synchronisation(dev, monkeypatch):
+    """After the first step for (graph, rows) — row sets, the two blocks, their schedules — a training step reads
+    nothing back to the host (the hooks of tests/test_fused_gpu.py)."""
+    from pygcn_amd import GCN, CSRGraph
+    from pygcn_amd.utils import rmat_graph
+    n, F = 200000, 256
+    rowptr, col, val = rmat_graph(n, 2000000, seed=4, device=dev)
+    g = CSRGraph(rowptr, col, val, (n, n))
+    x = torch.randn(n, F, device=dev)
+    y = torch.randint(0, F, (n,), device=dev)
+    idx = torch.arange(n // 20, device=dev)
+    y_idx = y[idx]
+    model = GCN(F, F, F, dropout=0.5).to(dev)
+    opt = torch.optim.Adam(model.parameters(), lr=0.01)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = torch.nn.functional.nll_loss(model(x, g, rows=idx, restrict_forward=True), y_idx)
+        loss.backward()
+        opt.step()
+        return loss
+    step()                                   # builds the row sets and blocks (one-off host reads)
+    torch.cuda.synchronize()
+    reads = []
+    for name in ("item", "tolist", "cpu", "__int__", "__bool__"):
+        real = getattr(torch.Tensor, name)
+        monkeypatch.setattr(torch.Tensor, name,
+                            (lambda r, nm: lambda t, *a, **k: (reads.append(nm) if t.is_cuda else None,
+                                                               r(t, *a, **k))[1])(real, name))
+    real_nonzero = torch.nonzero
+    monkeypatch.setattr(torch, "nonzero", lambda *a, **k: (reads.append("nonzero"), real_nonzero(*a, **k))[1])
+    l1 = step()
+    monkeypatch.undo()
+    assert reads == [], reads
+    assert torch.isfinite(l1).item()
+
+
+def test_restricted_step_allocates_nothing_of_full_height(dev):
+    """A condition, not a measurement.  Banded graph, N = 100 000, 8 entries per row (columns r-4 .. r+3), 100
+    consecutive loss rows: R2 has 107 <= 116 rows.  256 -> 256 -> 256: the peak allocation of a restricted step
+    above what is live before it stays below ONE [N, 256] fp32 tensor; the `rows=` route, whose forward pass is
+    full height, exceeds two."""
+    from pygcn_amd import GCN, CSRGraph, fused
+    n, F, deg = 100000, 256, 8
+    r = torch.arange(n, device=dev).repeat_interleave(deg)
+    col = ((r + torch.arange(-4, 4, device=dev).repeat(n)) % n).to(torch.int32)
+    col = col.view(n, deg).sort(1).values.reshape(-1).contiguous()
+    rowptr = (torch.arange(n + 1, device=dev) * deg).to(torch.int32)
+    g = CSRGraph(rowptr, col, torch.full((n * deg,), 1.0 / deg, device=dev), (n, n))
+    x = torch.randn(n, F, device=dev)
+    idx = torch.arange(5000, 5100, device=dev)
+    y = torch.randint(0, F, (100,), device=dev)
+    assert fused.row_sets(g, idx).n2 <= 116
+    model = GCN(F, F, F, dropout=0.5).to(dev)
+    model.train()
+    one = n * F * 4
+
+    def peak(restrict):
+        def step():
+            model.zero_grad(set_to_none=True)
+            torch.nn.functional.nll_loss(model(x, g, rows=idx, restrict_forward=restrict), y).backward()
+        step()                                    # (row sets, schedules, transposes: built once)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(dev)
+        live = torch.cuda.memory_allocated(dev)
+        step()
+        torch.cuda.synchronize()
+        return torch.cuda.max_memory_allocated(dev) - live
+    restricted, full = peak(True), peak(False)
+    print(f"peak above live: restricted {restricted} B, rows= {full} B, one [N, 256] fp32 tensor {one} B")
+    assert restricted < one
+    assert full > 2 * one
+
+
+def test_refusals_and_the_unchanged_default(dev, monkeypatch):
+    from pygcn_amd import GCN, CSRGraph, fused
+    from pygcn_amd.sharded import ShardedGraph
+    from pygcn_amd.utils import rmat_graph
+    n, F = 2000, 16
+    rowptr, col, val = rmat_graph(n, 10000, seed=9, device=dev)
+    g = CSRGraph(rowptr, col, val, (n, n))
+    x = torch.randn(n, F, device=dev)
+    idx = torch.arange(50, device=dev)
+    model = GCN(F, F, 4, dropout=0.5).to(dev)
+    coo = g.to_torch_csr().to_sparse_coo()
+    for adj, kw, word in ((g, dict(rows=None), "rows"), (g, dict(rows=idx, keep_full=True), "keep_full"),
+                          (coo.to_dense(), dict(rows=idx), "CSRGraph"), (coo, dict(rows=idx), "CSRGraph"),
+                          (object.__new__(ShardedGraph), dict(rows=idx), "ShardedGraph"),
+                          (g, dict(rows=idx, x=x.double()), "one-node")):
+        xx = kw.pop("x", x)
+        with pytest.raises(RuntimeError, match=word):
+            model(xx, adj, restrict_forward=True, **kw)
+    # without the flag: GCN2RowsFunction, as before
+    seen = []
+    real_rows, real_restricted = fused.gcn2_rows, fused.gcn2_rows_restricted
+    monkeypatch.setattr(fused, "gcn2_rows", lambda *a, **k: (seen.append("rows"), real_rows(*a, **k))[1])
+    monkeypatch.setattr(fused, "gcn2_rows_restricted",
+                        lambda *a, **k: (seen.append("restricted"), real_restricted(*a, **k))[1])
+    out = model(x, g, rows=idx)
+    assert seen == ["rows"] and type(out.grad_fn).__name__ == "GCN2RowsFunctionBackward"
+    out = model(x, g, rows=idx, restrict_forward=True)
+    assert seen == ["rows", "restricted"] and type(out.grad_fn).__name__ == "GCN2RestrictedFunctionBackward"
+
+
+def test_train_script_with_restrict_forward(dev):
+    """`python train.py --restrict_forward` for 5 epochs without dropout: training on idx_train and validation on
+    idx_val as restricted passes print G5's loss / accuracy fields, the trajectory captured from the imported
+    reference layer (--fastmode: validation with the training pass's parameters, as G5's loss_val was taken)."""
+    import os
+    import re
+    import subprocess
+    import sys
+    from conftest import ROOT
+    g5 = load_golden("g5_trajectory.npz")
+    r = subprocess.run([sys.executable, "train.py", "--epochs", "5", "--dropout", "0", "--fastmode", "--restrict_forward"],
+                       cwd=os.path.join(ROOT, "pygcn_amd"), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rows = re.findall(r"Epoch: (\d+) loss_train: ([\d.]+) acc_train: ([\d.]+) loss_val: ([\d.]+) "
+                      r"acc_val: ([\d.]+) time: [\d.]+s", r.stdout)
+    assert [int(x[0]) for x in rows] == [1, 2, 3, 4, 5], r.stdout[-2000:]
+    got = np.array([[float(v) for v in x[1:4]] for x in rows])
+    np.testing.assert_allclose(got[:, 0], g5["loss_train"][:5], atol=1.5e-4)   # printed with %.4f
+    np.testing.assert_allclose(got[:, 1], g5["acc_train"][:5], atol=1.5e-4)
+    np.testing.assert_allclose(got[:, 2], g5["loss_val"][:5], atol=1.5e-4)
+    assert "Optimization Finished!" in r.stdout and "Test set results:" in r.stdout
