@@ -478,6 +478,14 @@ int gcn_gemm_xw256_f32_b3(const float *X, int64_t ldx, const int32_t *x_rows, co
                           int64_t ldw, float *Y, int64_t ldy, int64_t M, float *y_absmax,
                           const gcn_gemm_epilogue *epilogue, void *workspace, size_t workspace_bytes,
                           void *stream);
+/* Y = log_softmax(X · W + bias) row by row (additive to ABI 26) — `F.log_softmax(x, dim=1)` (pygcn/models.py:52
+ * upstream) behind a last layer evaluated as (Â·h)·W + b: the contiguous-row kernel of gcn_gemm_xw256_f32_b3, whose
+ * waves own whole rows, normalises a finished tile in its registers before it is stored (hardware exp2 / log2 as
+ * in gcn_epilogue.log_softmax).  bias: DEVICE fp32 [256], 16-byte aligned, or NULL.  A row holding a NaN is NaN
+ * throughout; no other row is.  ldx, ldy < 2^21; workspace >= gcn_gemm_xw256_b3_workspace_bytes(). */
+int gcn_gemm_xw256_f32_b3_logsoftmax(const float *X, int64_t ldx, const float *W, int64_t ldw, const float *bias,
+                                     float *Y, int64_t ldy, int64_t M, void *workspace, size_t workspace_bytes,
+                                     void *stream);
 
 /*
  * Y[M, N] = X[M, K] · W[K, N] for bf16 storage (config C5: 128 -> 128): bf16 in / out, fp32
@@ -562,6 +570,26 @@ int gcn_rows_pack_values(int dtype, const void *src, int64_t ld, const int64_t *
 int gcn_rows_unpack(int dtype, const uint32_t *bits, const int64_t *offsets, const void *vals, int64_t m,
                     int64_t F, void *dst, int64_t ldd, void *stream);
 int gcn_bits_row_counts(const uint32_t *bits, int64_t m, int64_t words, int32_t *counts, void *stream);
+
+/*
+ * The FIXED-SLOT form of the same idea for the single-GPU layer-2 gather (additive to ABI 26): one 512-byte
+ * slot per 256-wide fp32 row, so a gather needs no offsets and reads half the bytes of the dense row.
+ *   slot r = words [128 r, 128 r + 128) of `slots`: four 128-byte sub-slots, one per column QUARTER in the lane
+ *   order of gcn_gemm_xw256_f32_b3's keep bits — quarter q holds columns 16 cb + 4 q + j (cb 0..15, j 0..3) at bit
+ *   4 cb + j.  Sub-slot q, 32 words: [0] [1] the 64-bit mask (bit set <=> the element's bit pattern is non-zero:
+ *   -0.0 is kept, the slot reproduces the row bit for bit), [2] the number of set bits, [3 ..] the non-zero values
+ *   in bit order.  A quarter with more than GCN_PACK512_CAPACITY set bits marks its row OVERFLOWED: its first 29
+ *   values are stored and a reader takes the dense row instead.  Words past the count are left unwritten.
+ * gcn_rows_pack512   : src [m, 256] fp32 (ld a multiple of 4, 16-byte aligned) -> slots [m][128] (16-byte aligned).
+ *   One streaming pass: reads 1 KiB and writes at most 512 bytes per row.
+ * gcn_spmm_csr_packed: C[n_rows, 256] = A · B with the rows of B gathered from `slots` (gcn_rows_pack512 of B);
+ *   B itself is read for overflowed rows only.  The same products in the same order as gcn_spmm_csr on B: the
+ *   result is bit-identical.  Workspace: gcn_spmm_workspace_bytes(plan, 256).  No epilogue.
+ */
+#define GCN_PACK512_CAPACITY 29
+int gcn_rows_pack512(const float *src, int64_t ld, int64_t m, uint32_t *slots, void *stream);
+int gcn_spmm_csr_packed(const gcn_csr_plan *plan, const uint32_t *slots, const float *B, int64_t ldb, float *C,
+                        int64_t ldc, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * ReLU + training-mode BatchNorm over the rows of a contiguous row-major [n_rows, F] activation —

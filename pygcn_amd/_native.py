@@ -96,6 +96,7 @@ SIGNATURES = {
     "gcn_gemm_xw256_f32_h2": (i, [p, i64, p, p, i64, p, i64, i64, p, p, gemm_ep_p, p, sz, p]),
     "gcn_gemm_xw256_b3_workspace_bytes": (sz, []),
     "gcn_gemm_xw256_f32_b3": (i, [p, i64, p, p, i64, p, i64, i64, p, gemm_ep_p, p, sz, p]),
+    "gcn_gemm_xw256_f32_b3_logsoftmax": (i, [p, i64, p, i64, p, p, i64, i64, p, sz, p]),
     "gcn_gemm_bf16_workspace_bytes": (sz, [i64, i64]),
     "gcn_gemm_xw_bf16": (i, [p, i64, p, i64, p, i64, i64, i64, i64, gemm_ep_p, p, sz, p]),
     "gcn_gemm_atg256_workspace_bytes": (sz, [i64]),
@@ -108,6 +109,8 @@ SIGNATURES = {
     "gcn_rows_pack_values": (i, [i, p, i64, p, i64, i64, p, p, p]),
     "gcn_rows_unpack": (i, [i, p, p, p, i64, i64, p, i64, p]),
     "gcn_bits_row_counts": (i, [p, i64, i64, p, p]),
+    "gcn_rows_pack512": (i, [p, i64, i64, p, p]),
+    "gcn_spmm_csr_packed": (i, [plan_p, p, p, i64, p, i64, p, sz, p]),
     "gcn_bn_workspace_bytes": (sz, [i64, i64, i]),
     "gcn_bn_stats": (i, [i, p, i64, i64, i, f32, p, p, p, p, sz, p]),
     "gcn_bn_apply": (i, [i, p, p, i64, i64, i, p, p, p, p, p]),

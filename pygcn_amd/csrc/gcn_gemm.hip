@@ -1037,9 +1037,13 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_s16_kernel(
     // EPI as in gemm_xw256_h2_kernel: 0 plain, 2 backward mask, 1 bias, 4 + ReLU, 5 + dropout at 1/2, 6 + dropout at p;
     // 3: backward mask from KEEP BITS (H2Epi::mask_bits: 8 bytes per lane and tile instead of 16 x 16)
     // BITS (with ReLU): the launch also writes `out > 0` as one bit per element (H2Epi::keep_bits_out)
+    // 7: bias + row-wise log_softmax (the model's last line, `F.log_softmax(x, dim=1)`, for a last layer evaluated
+    //    as (Â·h)·W + b): a wave owns whole rows — row n16 lives in the lanes (n16, q = 0..3) x 16 column blocks —
+    //    so the finished tile is normalised in its registers before its first column block leaves (lsm_tile)
+    constexpr bool LSM = EPI == 7;
     constexpr bool FWD_EPI = EPI == 1 || EPI >= 4, MASKED = EPI == 2, MASK_BITS = EPI == 3;
     static_assert(!BITS || EPI == 4 || EPI == 5, "keep bits belong to the ReLU epilogues");
-    constexpr bool RELU = EPI >= 4, DROP1 = EPI == 5, DROP16 = EPI == 6;
+    constexpr bool RELU = EPI >= 4 && EPI <= 6, DROP1 = EPI == 5, DROP16 = EPI == 6;
     static_assert(kWaves == 8, "written for eight waves");
     constexpr int kSt = kS16StageBytes, kWShare = kSt / kWaves;          // a wave's part of a stage: 6 KiB
     extern __shared__ __attribute__((aligned(16))) unsigned char s16_lds[];   // [W stage 0][W stage 1][X rings][bias]
@@ -1141,7 +1145,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_s16_kernel(
     [[maybe_unused]] int64_t pmask_row = 0;                      // masked form: the mask row of this lane's prev row
     auto finish = [&](int cb, f32x4 v, const f32x4 &mk, int64_t drow) __attribute__((always_inline)) -> f32x4 {
         const int f = 16 * cb + 4 * q;                           // first of this lane's 4 columns
-        if (FWD_EPI) {
+        if (FWD_EPI && !LSM) {                                   // (LSM: lsm_tile added the bias)
             const f32x4 b4 = *(const f32x4 *)(bias_lds + f);
             v.x += b4.x; v.y += b4.y; v.z += b4.z; v.w += b4.w;
         }
@@ -1213,6 +1217,39 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_s16_kernel(
             h2_philox((uint32_t)drow, (uint32_t)(drow >> 32), cw, 0u, seed_k0, seed_k1, r1);
         }
         if (MASKED) pmask_row = row >= M ? 0 : (ep.mask_rows != nullptr ? (int64_t)ep.mask_rows[row] : row);
+    };
+    // EPI 7, once per finished tile, on `prev` in place: + bias, then x - (max + log Σ exp(x - max)) over the row.
+    // 64 of a row's 256 values are this lane's; the other three quarters sit 16, 32 and 48 lanes away.  __expf /
+    // __logf as in the SpMM's log_softmax store (gcn_spmm.hip store_out): hardware exp2 / log2, arguments <= 0,
+    // Σ in [1, 256].  fmaxf skips a NaN, exp(NaN - max) does not: a row holding one is NaN throughout, no other is.
+    auto lsm_tile = [&]() {
+        if (!LSM) return;
+        float m = -INFINITY;
+#pragma unroll
+        for (int cb = 0; cb < 16; ++cb) {
+            const f32x4 b4 = *(const f32x4 *)(bias_lds + 16 * cb + 4 * q);
+            f32x4 v = prev[cb];
+            v.x += b4.x; v.y += b4.y; v.z += b4.z; v.w += b4.w;
+            prev[cb] = v;
+            m = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+        }
+        m = fmaxf(m, __shfl_xor(m, 16, 64));
+        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        float se = 0.f;
+#pragma unroll
+        for (int cb = 0; cb < 16; ++cb) {
+            const f32x4 v = prev[cb];
+            se += (__expf(v.x - m) + __expf(v.y - m)) + (__expf(v.z - m) + __expf(v.w - m));
+        }
+        se += __shfl_xor(se, 16, 64);
+        se += __shfl_xor(se, 32, 64);
+        const float lse = m + __logf(se);
+#pragma unroll
+        for (int cb = 0; cb < 16; ++cb) {
+            f32x4 v = prev[cb];
+            v.x -= lse; v.y -= lse; v.z -= lse; v.w -= lse;
+            prev[cb] = v;
+        }
     };
     [[maybe_unused]] f32x4 mk[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};   // masked form: the next pair's masks
     auto mask_load = [&](int pair) {
@@ -1343,6 +1380,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_s16_kernel(
         }
 #pragma unroll
         for (int cb = 0; cb < 16; ++cb) prev[cb] = acc[cb];
+        lsm_tile();
         ptile = tile;
         have_prev = true;
         st_n += 1;
@@ -2295,6 +2333,8 @@ template <class... K> struct XwList {
 using XwKernels = XwList<Xw<0, 0>, Xw<0, 1>, Xw<0, 2>, Xw<0, 4>, Xw<0, 5>, Xw<0, 6>,
                          Xw<1, 0>, Xw<1, 1>, Xw<1, 2>, Xw<1, 4>, Xw<1, 5>, Xw<1, 6>,
                          Xw<2, 0>, Xw<2, 1>, Xw<2, 2>, Xw<2, 3>, Xw<2, 4>, Xw<2, 5>, Xw<2, 4, true>, Xw<2, 5, true>>;
+// ... and the one gcn_gemm_xw256_f32_b3_logsoftmax launches (bias + row-wise log_softmax, contiguous rows only)
+using XwLogSoftmax = XwList<Xw<2, 7>>;
 
 }   // namespace
 
@@ -2303,7 +2343,7 @@ using XwKernels = XwList<Xw<0, 0>, Xw<0, 1>, Xw<0, 2>, Xw<0, 4>, Xw<0, 5>, Xw<0,
 static int xw256_launch(const char *who, int sch, const float *X, int64_t ldx, const int32_t *x_rows, const float *W,
                         int64_t ldw, float *Y, int64_t ldy, int64_t M, const float *x_absmax_bound,
                         float *y_absmax, const gcn_gemm_epilogue *epi, void *workspace,
-                        size_t workspace_bytes, void *stream)
+                        size_t workspace_bytes, void *stream, bool log_softmax = false)
 {
     char msg[256];
     auto named = [&](const char *what) -> const char * {
@@ -2353,12 +2393,16 @@ static int xw256_launch(const char *who, int sch, const float *X, int64_t ldx, c
     // 3 backward mask from keep bits, 1 bias, 4 bias + ReLU, 5 + dropout at p = 1/2 (one-bit keep fields),
     // 6 + dropout at another p
     const bool fwd = ep.bias != nullptr || ep.relu || ep.drop_thresh != 0u;
-    const int variant = !fwd ? (ep.mask_bits != nullptr ? 3 : (ep.mask_src != nullptr ? 2 : 0))
-                             : (!ep.relu ? 1 : (ep.drop_thresh == 0u ? 4 : (ep.drop_thresh == 32768u ? 5 : 6)));
+    // 7 bias + row-wise log_softmax (gcn_gemm_xw256_f32_b3_logsoftmax: contiguous rows only)
+    const int variant = log_softmax ? 7
+                        : !fwd ? (ep.mask_bits != nullptr ? 3 : (ep.mask_src != nullptr ? 2 : 0))
+                               : (!ep.relu ? 1 : (ep.drop_thresh == 0u ? 4 : (ep.drop_thresh == 32768u ? 5 : 6)));
     // the three-part scheme on contiguous rows runs gemm_xw256_s16_kernel (128-row tiles, stores under the next
     // tile's MFMAs).  (It addresses a tile's rows as 32-bit offsets from the tile origin, takes no row list, and
     // has no instantiation for dropout at p != 1/2)
     const bool s16 = sch == 1 && x_rows == nullptr && variant != 6 && ldx < (1 << 21) && ldy < (1 << 21);
+    if (log_softmax && !s16)
+        return gcn_internal_fail(GCN_E_BADARG, named(": row pitches must be below 2^21 elements"));
     // (the one-bit mask exists in the contiguous-row kernel's lane order only: a launch that cannot take that kernel
     //  must be given mask_src / no keep_bits_out — refuse rather than ignore)
     if ((ep.mask_bits != nullptr || ep.keep_bits_out != nullptr) &&
@@ -2377,7 +2421,8 @@ static int xw256_launch(const char *who, int sch, const float *X, int64_t ldx, c
                            (uint16_t *)((unsigned char *)workspace + kH2HeaderBytes));
     static bool raised = false;          // (once, on the first call: a later one may be inside graph capture;
     if (!raised) {                       //  idempotent, a benign race sets it twice)
-        const hipError_t ae = XwKernels::set_lds();
+        hipError_t ae = XwKernels::set_lds();
+        if (ae == hipSuccess) ae = XwLogSoftmax::set_lds();
         if (ae != hipSuccess) return gcn_internal_fail_hip((int)ae, named(": LDS size"));
         raised = true;
     }
@@ -2385,7 +2430,7 @@ static int xw256_launch(const char *who, int sch, const float *X, int64_t ldx, c
     const XwLaunch a = {s16 ? 2 : sch, variant, ep.keep_bits_out != nullptr && fwd,
                         (unsigned)std::min<int64_t>(tiles, kXwGrid), s, X, ldx, x_rows,
                         (const unsigned char *)workspace, x_absmax_bound, Y, ldy, M, (uint32_t *)y_absmax, ep};
-    if (!XwKernels::launch(a)) return gcn_internal_fail(GCN_E_BADARG, named(": no kernel for these options"));
+    if (!(log_softmax ? XwLogSoftmax::launch(a) : XwKernels::launch(a))) return gcn_internal_fail(GCN_E_BADARG, named(": no kernel for these options"));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return gcn_internal_fail_hip((int)e, named(" launch"));
     return 0;
@@ -2409,6 +2454,16 @@ int gcn_gemm_xw256_f32_b3(const float *X, int64_t ldx, const int32_t *x_rows, co
 {
     return xw256_launch("gcn_gemm_xw256_f32_b3", 1, X, ldx, x_rows, W, ldw, Y, ldy, M, nullptr, y_absmax, epi,
                         workspace, workspace_bytes, stream);
+}
+
+int gcn_gemm_xw256_f32_b3_logsoftmax(const float *X, int64_t ldx, const float *W, int64_t ldw, const float *bias,
+                                     float *Y, int64_t ldy, int64_t M, void *workspace, size_t workspace_bytes,
+                                     void *stream)
+{
+    gcn_gemm_epilogue epi = {};
+    epi.bias = bias;
+    return xw256_launch("gcn_gemm_xw256_f32_b3_logsoftmax", 1, X, ldx, nullptr, W, ldw, Y, ldy, M, nullptr, nullptr,
+                        &epi, workspace, workspace_bytes, stream, true);
 }
 
 size_t gcn_gemm_bf16_workspace_bytes(int64_t K, int64_t N)

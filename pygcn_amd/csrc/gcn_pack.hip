@@ -199,6 +199,56 @@ __global__ __launch_bounds__(256) void bits_count_kernel(const uint32_t *__restr
     if (r < m && sub == 0) counts[r] = c;
 }
 
+// ------------------------------------------------------------------------------------------------
+// FIXED-SLOT form for the single-GPU layer-2 gather (gcn_spmm_csr_packed): one 512-byte slot per 256-wide fp32
+// row, four 128-byte sub-slots, one per column QUARTER in the lane order of the 256-wide GEMM's keep bits —
+// quarter q holds columns 16 cb + 4 q + j (cb 0..15, j 0..3), bit 4 cb + j.  A sub-slot is 32 words:
+//     [0] [1]   the 64-bit mask, bit set <=> the element's BIT PATTERN is non-zero (-0.0 is kept: the slot
+//               reproduces the row bit for bit)
+//     [2]       the number of set bits; more than GCN_PACK512_CAPACITY (29) marks the quarter — and with it the
+//               row — as overflowed: its first 29 values are stored, a reader takes the dense row instead
+//     [3 ..]    the non-zero values in bit order (words past the count are left unwritten)
+// One wave per row, 16 lanes per quarter: lane (q, i) reads the 16 bytes of columns 16 i + 4 q .. + 3 (the wave
+// reads the whole 1-KiB row), the quarter's mask is an OR over its 16 lanes (DPP), a value's place its rank.
+constexpr int kPack512Cap = GCN_PACK512_CAPACITY;
+
+__device__ __forceinline__ uint32_t or16(uint32_t v)       // OR over each row of 16 lanes
+{
+    v = or8(v);
+    v |= dpp_u<0x140>(v);
+    return v;
+}
+
+__global__ __launch_bounds__(kWave *kRowsPerBlock) void pack512_kernel(const float *__restrict__ src, int64_t ld,
+                                                                       int64_t m, uint32_t *__restrict__ slots)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t r = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+    if (r >= m) return;
+    const int q = lane >> 4, i = lane & 15;
+    const uint4 v = *(const uint4 *)(src + r * ld + 16 * i + 4 * q);
+    const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+    uint32_t nib = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) nib |= (x[j] != 0u ? 1u : 0u) << j;
+    const uint32_t lo = or16(i < 8 ? nib << (4 * i) : 0u), hi = or16(i >= 8 ? nib << (4 * (i - 8)) : 0u);
+    const unsigned long long mask = ((unsigned long long)hi << 32) | lo;
+    int rank = __builtin_popcountll(mask & ((1ull << (4 * i)) - 1ull));
+    uint32_t *sub = slots + r * 128 + 32 * q;
+    if (i == 0) {
+        sub[0] = lo;
+        sub[1] = hi;
+        sub[2] = (uint32_t)__builtin_popcountll(mask);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if ((nib >> j) & 1u) {
+            if (rank < kPack512Cap) sub[3 + rank] = x[j];
+            ++rank;
+        }
+    }
+}
+
 int check(const char *who, int dtype, int64_t m, int64_t F, int64_t ld)
 {
     if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16) return gcn_internal_fail(GCN_E_BADARG, who);
@@ -266,6 +316,20 @@ int gcn_rows_unpack(int dtype, const uint32_t *bits, const int64_t *offsets, con
         hipLaunchKernelGGL(unpack_kernel<bf16_t>, grid, block, 0, s, bits, offsets, (const bf16_t *)vals, m, (int)F, (bf16_t *)dst, ldd);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, "gcn_rows_unpack launch");
+}
+
+int gcn_rows_pack512(const float *src, int64_t ld, int64_t m, uint32_t *slots, void *stream)
+{
+    if (m < 0 || ld < 256 || ld % 4 != 0) return gcn_internal_fail(GCN_E_BADARG, "gcn_rows_pack512: bad sizes (256 columns, ld a multiple of 4)");
+    if (m == 0) return 0;
+    if (src == nullptr || slots == nullptr) return gcn_internal_fail(GCN_E_BADARG, "gcn_rows_pack512: NULL pointer");
+    if ((((uintptr_t)src) | ((uintptr_t)slots)) % 16 != 0)
+        return gcn_internal_fail(GCN_E_ALIGN, "gcn_rows_pack512: 16-byte alignment required");
+    if ((m + kRowsPerBlock - 1) / kRowsPerBlock > INT32_MAX) return gcn_internal_fail(GCN_E_BADARG, "gcn_rows_pack512: too many rows");
+    const dim3 grid((unsigned)((m + kRowsPerBlock - 1) / kRowsPerBlock)), block(kWave * kRowsPerBlock);
+    hipLaunchKernelGGL(pack512_kernel, grid, block, 0, (hipStream_t)stream, src, ld, m, slots);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, "gcn_rows_pack512 launch");
 }
 
 int gcn_bits_row_counts(const uint32_t *bits, int64_t m, int64_t words, int32_t *counts, void *stream)

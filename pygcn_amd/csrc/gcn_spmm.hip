@@ -105,6 +105,7 @@ struct KParams {
     const uint32_t *csel;       // optional bitmap over output rows: clear bit = row not wanted
     int32_t cskip;              // with cflag: all-zero rows are not stored
     uint32_t *cabsmax;          // optional output: max |stored value| as BITS (atomic max; inf / NaN sort on top)
+    const void *packed;         // spmm_wide_packed_kernel: the 512-byte slots of the rows of B (gcn_rows_pack512)
 };
 
 // ------------------------------------------------------------------------------------------
@@ -582,6 +583,167 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void spmm_wide_kernel(KParam
     wide_stream<T, VEC, D, true, FLAGS, XEPI>(p, p.col + ea, p.val + ea, ne, lane, ld_off_bytes, acc, rel_end,
                                  nr, (int64_t)ra, f, act, bias, amax);
     publish_absmax<XEPI>(p, amax);
+}
+
+// ------------------------------------------------------------------------------------------
+// WIDE kernel on PACKED rows (gcn_spmm_csr_packed): the 256-wide fp32 operand is gathered from the 512-byte
+// slots of gcn_rows_pack512 (gcn_pack.hip: four 128-byte sub-slots, one per column quarter: 64-bit mask,
+// count, non-zero values in bit order) — half the bytes of a dense row per stored entry.
+//   * per stored entry ONE 8-byte buffer load per lane at the lane-static offset 8 * lane: lane (q, i) =
+//     (lane >> 4, lane & 15) holds words 2i, 2i + 1 of sub-slot q; the ladder is that of wide_stream (D loads in
+//     flight, no branch, a slot past the tile has num_records 0 and reads zeros = an empty mask);
+//   * lane (q, i) OWNS columns 16 i + 4 q .. + 3 = bits 4i .. 4i + 3 of its quarter: the mask and the count come
+//     from lanes 0 / 1 of its row of 16 (DPP row broadcast), its values start at word 3 + popcount(mask below
+//     bit 4i) and span at most three lanes of the row: five ds_bpermute, then selects by the nibble;
+//   * the same fmaf per (entry, column) in the same order as the dense launch — a cleared bit contributes
+//     fmaf(a, 0, acc) as the dense zero does — so the result is bit-identical;
+//   * an entry whose slot reports an overflowed quarter (count > 29; wave-uniform test on the loaded words)
+//     takes its four values from the dense row instead, in place: the order of the sum does not change.
+// Row bookkeeping, long-row chunks (fp32 partial slab, spmm_long_reduce_kernel) and the store are wide_stream's;
+// only the column a lane owns differs (the store is still 16 bytes per lane, one full row per wave).
+// ------------------------------------------------------------------------------------------
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ u32x2 slot_load8(uint64_t base, uint32_t nbytes, uint32_t voff)
+{
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
+    void *pb = (void *)(((uint64_t)hi << 32) | lo);
+    __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(pb, 0, nbytes, 0x00020000);
+    return __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, 0, 0);
+}
+
+template <int N> __device__ __forceinline__ uint32_t row_bcast(uint32_t v)    // lane N of every row of 16 lanes
+{
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x150 + N, 0xF, 0xF, true);   // (every lane has a source)
+}
+
+constexpr int kPackSlotBytes = 512;
+constexpr uint32_t kPackCap = GCN_PACK512_CAPACITY;
+
+template <int D, bool ROWS>
+__device__ __forceinline__ void packed_stream(const KParams &p, const int32_t *__restrict__ colp,
+                                              const float *__restrict__ valp, int ne, int lane, float (&acc)[4],
+                                              int rel_end, int nr, int64_t row0, int f, const float (&bias)[4])
+{
+    const int i = lane & 15;
+    const uint32_t ldb_bytes = (uint32_t)(p.ldb * 4);                    // the dense rows (overflowed slots)
+    const uint32_t voff = (uint32_t)lane * 8u;
+    const unsigned long long below = (1ull << (4 * i)) - 1ull;
+    const int row_lane0 = (lane & 48) << 2;              // 4 * the first lane of this lane's row of 16
+    int r = 0;
+    int rend = ROWS ? readlane_i(rel_end, 0) : INT_MAX;
+    auto consume = [&](int e, const u32x2 &raw, float a, int c) {
+        if (ROWS) {
+            while (e >= rend) {   // row finished (loop: rows without stored entries follow)
+                store_out<float, 4, kWave, 0>(p, row0 + r, f, true, acc, bias);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[k] = 0.f;
+                ++r;
+                rend = readlane_i(rel_end, r);
+            }
+        }
+        const uint32_t mlo = row_bcast<0>(raw.x), mhi = row_bcast<0>(raw.y), cnt = row_bcast<1>(raw.x);
+        float x[4];
+        if (__ballot(cnt > kPackCap) != 0ull) {      // wave-uniform and rare: a quarter did not fit its sub-slot
+            const u32x4 d = row_load16((uint64_t)p.B + (uint64_t)(uint32_t)c * ldb_bytes, 1024u, (uint32_t)f * 4u);
+            Elem<float, 4>::unpack(__builtin_bit_cast(f32x4, d), x);
+        } else {
+            const unsigned long long m = ((unsigned long long)mhi << 32) | mlo;
+            const uint32_t nib = (uint32_t)(m >> (4 * i)) & 0xFu;
+            const int w0 = 3 + __builtin_popcountll(m & below);          // word of this lane's first value
+            // ... in lane w0 >> 1 of the row of 16, and the next two (byte addresses of ds_bpermute: 4 * lane)
+            const int w2 = w0 << 1;
+            const int a0 = row_lane0 | (w2 & 60), a1 = row_lane0 | ((w2 + 4) & 60), a2 = row_lane0 | ((w2 + 8) & 60);
+            const int s0 = __builtin_amdgcn_ds_bpermute(a0, (int)raw.x), s1 = __builtin_amdgcn_ds_bpermute(a0, (int)raw.y);
+            const int s2 = __builtin_amdgcn_ds_bpermute(a1, (int)raw.x), s3 = __builtin_amdgcn_ds_bpermute(a1, (int)raw.y);
+            const int s4 = __builtin_amdgcn_ds_bpermute(a2, (int)raw.x);
+            // single-level selects (one v_cndmask each): first the four words from w0 on (an odd w0 starts in
+            // the upper word of its lane), then, bit by bit of the nibble, "take the head of the queue if the
+            // bit is set" — a cleared bit leaves +0.0
+            const bool odd = (w0 & 1) != 0;
+            float q0 = __int_as_float(odd ? s1 : s0), q1 = __int_as_float(odd ? s2 : s1),
+                  q2 = __int_as_float(odd ? s3 : s2), q3 = __int_as_float(odd ? s4 : s3);
+            const bool b0 = (nib & 1u) != 0u, b1 = (nib & 2u) != 0u, b2 = (nib & 4u) != 0u, b3 = (nib & 8u) != 0u;
+            x[0] = b0 ? q0 : 0.f;
+            q0 = b0 ? q1 : q0; q1 = b0 ? q2 : q1; q2 = b0 ? q3 : q2;
+            x[1] = b1 ? q0 : 0.f;
+            q0 = b1 ? q1 : q0; q1 = b1 ? q2 : q1;
+            x[2] = b2 ? q0 : 0.f;
+            q0 = b2 ? q1 : q0;
+            x[3] = b3 ? q0 : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = fmaf(a, x[k], acc[k]);
+    };
+
+    for (int t = 0; t < ne; t += kWave) {
+        const int cnt = min(kWave, ne - t);
+        int cv = 0;
+        float vv = 0.f;   // lanes >= cnt keep value 0: slots past the tile add 0 * 0
+        if (lane < cnt) {
+            cv = colp[t + lane];
+            vv = valp[t + lane];
+        }
+        for (int k = 0; k < cnt; k += D) {
+            u32x2 x[D];
+            int cc[D];
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                const bool ok = k + j < cnt;
+                cc[j] = readlane_i(cv, k + j);   // k + j <= 63 always (k <= 56)
+                x[j] = slot_load8((uint64_t)p.packed + (uint64_t)(uint32_t)cc[j] * (uint64_t)kPackSlotBytes,
+                                  ok ? (uint32_t)kPackSlotBytes : 0u, voff);
+            }
+#pragma unroll
+            for (int j = 0; j < D; ++j)
+                consume(min(t + k + j, ne - 1), x[j], readlane_f(vv, k + j), cc[j]);
+        }
+    }
+    if (ROWS) {
+        while (r < nr) {   // last row of the item and any trailing empty rows
+            store_out<float, 4, kWave, 0>(p, row0 + r, f, true, acc, bias);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[k] = 0.f;
+            ++r;
+        }
+    }
+}
+
+template <typename IdxT, int D>
+__global__ __launch_bounds__(kWave *kWavesPerBlock) void spmm_wide_packed_kernel(KParams p)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const int item =
+        blockIdx.x * kWavesPerBlock + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (item >= p.n_total) return;
+    const int f = 16 * (lane & 15) + 4 * (lane >> 4);          // (F = 256: every lane holds four columns)
+    const IdxT *__restrict__ rp = (const IdxT *)p.rowptr;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f}, bias[4] = {0.f, 0.f, 0.f, 0.f};
+
+    if (item < p.n_chunks) {
+        // ---- one chunk of a long row -> fp32 partial slab
+        const int row = p.chunk_row[item];
+        const int64_t e0 = p.chunk_e0[item];
+        const int64_t e1 = min(e0 + (int64_t)p.long_thresh, (int64_t)rp[row + 1]);
+        packed_stream<D, false>(p, p.col + e0, p.val + e0, (int)(e1 - e0), lane, acc, 0, 0, 0, f, bias);
+        float *dst = p.partial + (int64_t)item * p.F + f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) dst[k] = acc[k];
+        return;
+    }
+    // ---- a row-batch item: rows [ra, rb), <= 64 rows, contiguous stored entries
+    const int it = item - p.n_chunks;
+    const int ra = p.items[2 * it], rb = p.items[2 * it + 1];
+    const int nr = rb - ra;
+    const int64_t ea = (int64_t)rp[ra];
+    const int rel_end = (lane < nr) ? (int)((int64_t)rp[ra + 1 + lane] - ea) : 0;
+    const int ne = readlane_i(rel_end, nr - 1);
+    if (p.bias != nullptr) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) bias[k] = p.bias[f + k];
+    }
+    packed_stream<D, true>(p, p.col + ea, p.val + ea, ne, lane, acc, rel_end, nr, (int64_t)ra, f, bias);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1236,7 +1398,13 @@ int spmm_typed(const gcn_csr_plan *plan, KParams &kp, hipStream_t s)
         return fail(GCN_E_BADARG, "gcn_spmm_csr_ep: log_softmax needs the row inside one wavefront "
                                   "(F <= 64, or 16-byte aligned operands with F/lane width <= 64)");
     if (kp.n_total > 0) {
-        if (vec_ok) {
+        if (kp.packed != nullptr) {
+            if constexpr (sizeof(T) == 4) {      // (fp32, F = 256, aligned: gcn_spmm_csr_packed checked)
+                const dim3 grid(nblk, 1), block(kWave * kWavesPerBlock);
+                if (is64) hipLaunchKernelGGL((spmm_wide_packed_kernel<int64_t, 8>), grid, block, 0, s, kp);
+                else hipLaunchKernelGGL((spmm_wide_packed_kernel<int32_t, 8>), grid, block, 0, s, kp);
+            }
+        } else if (vec_ok) {
             const int lanes = F / VECW;
             if (lanes > 32) {
                 dim3 grid(nblk, (unsigned)((lanes + kWave - 1) / kWave));
@@ -1466,9 +1634,10 @@ size_t gcn_spmm_workspace_bytes(const gcn_csr_plan *plan, int64_t F)
     return (size_t)plan->n_chunks * (size_t)F * sizeof(float);
 }
 
-int gcn_spmm_csr_ep(const gcn_csr_plan *plan, int dtype, const void *B, int64_t ldb, void *C,
-                    int64_t ldc, int64_t F, const gcn_epilogue *ep, void *workspace,
-                    size_t workspace_bytes, void *stream)
+// gcn_spmm_csr_ep, and (`packed` != NULL: the slots of the rows of B) gcn_spmm_csr_packed
+static int spmm_csr_impl(const gcn_csr_plan *plan, int dtype, const void *B, int64_t ldb, void *C,
+                         int64_t ldc, int64_t F, const gcn_epilogue *ep, void *workspace,
+                         size_t workspace_bytes, void *stream, const void *packed)
 {
     const float *bias = ep ? ep->bias : nullptr;
     const int relu = ep ? ep->relu : 0;
@@ -1499,6 +1668,7 @@ int gcn_spmm_csr_ep(const gcn_csr_plan *plan, int dtype, const void *B, int64_t 
         return fail(GCN_E_WORKSPACE, "gcn_spmm_csr_ep: workspace too small");
 
     KParams kp;
+    kp.packed = packed;
     kp.rowptr = plan->rowptr;
     kp.col = plan->col;
     kp.val = plan->val;
@@ -1545,6 +1715,22 @@ int gcn_spmm_csr_ep(const gcn_csr_plan *plan, int dtype, const void *B, int64_t 
     hipStream_t s = (hipStream_t)stream;
     if (dtype == GCN_DTYPE_F32) return spmm_typed<float, 4>(plan, kp, s);
     return spmm_typed<bf16_t, 8>(plan, kp, s);
+}
+
+int gcn_spmm_csr_ep(const gcn_csr_plan *plan, int dtype, const void *B, int64_t ldb, void *C,
+                    int64_t ldc, int64_t F, const gcn_epilogue *ep, void *workspace,
+                    size_t workspace_bytes, void *stream)
+{
+    return spmm_csr_impl(plan, dtype, B, ldb, C, ldc, F, ep, workspace, workspace_bytes, stream, nullptr);
+}
+
+int gcn_spmm_csr_packed(const gcn_csr_plan *plan, const uint32_t *slots, const float *B, int64_t ldb, float *C,
+                        int64_t ldc, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (slots == nullptr || B == nullptr) return fail(GCN_E_BADARG, "gcn_spmm_csr_packed: slots or B is NULL");
+    if ((((uintptr_t)slots) | ((uintptr_t)B) | ((uintptr_t)C)) % 16 != 0 || ldb % 4 != 0 || ldc % 4 != 0)
+        return fail(GCN_E_ALIGN, "gcn_spmm_csr_packed: 16-byte aligned slots and rows required");
+    return spmm_csr_impl(plan, GCN_DTYPE_F32, B, ldb, C, ldc, 256, nullptr, workspace, workspace_bytes, stream, slots);
 }
 
 int gcn_spmm_csr(const gcn_csr_plan *plan, int dtype, const void *B, int64_t ldb, void *C,

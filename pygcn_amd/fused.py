@@ -42,6 +42,7 @@ with the route's own sparse product between them: `_gcn2_backward_rows` (the blo
 pygcn_amd/sharded_fused.py (the block plus a halo of gradient rows), and, for the first stage, the
 last-layer branch of `GraphConvFunction._backward_rows` (pygcn_amd/spmm.py).
 """
+import os
 import weakref
 
 import torch
@@ -197,6 +198,44 @@ def input_product(graph, x):
     return z
 
 
+# ON by default (22.2 -> 21.0 ms of kernels, 51.7 -> 49.9 ms per epoch at C4).  PYGCN_PACKED_HIDDEN=0 in
+# the environment starts with the dense route: an A/B switch for bench.py, which has no flag for it.
+_PACKED_HIDDEN = os.environ.get("PYGCN_PACKED_HIDDEN", "1") != "0"
+
+
+def set_packed_hidden(enabled):
+    """Layer 2 of the training-mode forward pass as (Â·h1)·W2 over PACKED hidden rows:
+
+        P    = rows_pack512(h1)                     512-byte slots: masks + the non-zero values (>= 75 % of h1 is 0)
+        z2   = Â·P                                  the wide SpMM gathering half the bytes per stored entry
+        logp = log_softmax(z2·W2 + b2)              the contiguous-row GEMM with the log_softmax epilogue
+
+    instead of log_softmax(Â·(h1·W2) + b2).  Taken where packed_hidden_applies(); every other call, eval mode
+    and dropout 0 keep the dense route.  The backward pass is the same for both (h1 itself is still written)."""
+    global _PACKED_HIDDEN
+    _PACKED_HIDDEN = bool(enabled)
+
+
+def packed_hidden():
+    """Is the packed route switched on (set_packed_hidden)?"""
+    return _PACKED_HIDDEN
+
+
+def packed_hidden_applies(h1, w2, b2, dropout_p):
+    """fp32, hidden width 256, 256 classes, dropout > 0 (a training-mode pass: h1 is mostly zeros) and the
+    hand-written three-part GEMMs."""
+    return (_PACKED_HIDDEN and dropout_p > 0.0 and h1.dtype == torch.float32 and _gemm.gemm_scheme() == "bf16x3"
+            and tuple(w2.shape) == (256, 256) and w2.dtype == torch.float32 and w2.stride(1) == 1
+            and _spmm.rows_pack512_usable(h1) and h1.stride(0) < (1 << 21)
+            and (b2 is None or (b2.dtype == torch.float32 and b2.is_contiguous() and b2.data_ptr() % 16 == 0)))
+
+
+def _layer2_packed(graph, h1, w2, b2):
+    """logp by the packed route, or None where the log_softmax GEMM declines the operands."""
+    z2 = spmm_csr(graph, packed=_spmm.rows_pack512(h1))
+    return _gemm.gemm_xw256_log_softmax(z2, w2, b2)
+
+
 def _gcn2_forward(ctx, x, w1, b1, w2, b2, graph, dropout_p, seed):
     """Forward pass shared by the one-node functions: (tensor saved in place of x, h1, logp).
     Fills ctx.scale / x_bound / z_bound / h_bound / reassoc / has_bias / bias_dtypes."""
@@ -242,7 +281,9 @@ def _gcn2_forward(ctx, x, w1, b1, w2, b2, graph, dropout_p, seed):
                 h_bound = h_bound + b1.detach().abs().max().float()
             h_bound = h_bound * (1.0001 * ctx.scale)
     ctx.h_bound = h_bound
-    logp = spmm_csr(graph, _dense_forward(h1, w2, h_bound), bias=b2, log_softmax=True)
+    logp = _layer2_packed(graph, h1, w2, b2) if packed_hidden_applies(h1, w2, b2, dropout_p) else None
+    if logp is None:
+        logp = spmm_csr(graph, _dense_forward(h1, w2, h_bound), bias=b2, log_softmax=True)
     ctx.has_bias = (b1 is not None, b2 is not None)
     ctx.bias_dtypes = (b1.dtype if b1 is not None else None, b2.dtype if b2 is not None else None)
     return (z if ctx.reassoc else x), h1, logp

@@ -185,6 +185,27 @@ def gemm_xw256(X, W, x_bound=None, y_absmax=None, rows=None, mask_src=None, mask
     return Y
 
 
+def gemm_xw256_log_softmax(X, W, bias=None):
+    """log_softmax(X[M,256] · W[256,256] + bias, dim=1) in ONE launch of the contiguous-row three-part kernel
+    (C-ABI gcn_gemm_xw256_f32_b3_logsoftmax: the finished tile is normalised in registers before it is stored) —
+    the end of a last layer evaluated as (Â·h)·W + b.  None where the kernel does not apply (another scheme,
+    shape, pitch or alignment): the caller then takes another route."""
+    if (_gemm_scheme != "bf16x3" or not X.is_cuda or not _mfma_rows(X, torch.float32, 256, 4)
+            or X.stride(0) >= (1 << 21) or W.dtype != torch.float32 or tuple(W.shape) != (256, 256)
+            or W.stride(1) != 1 or W.device != X.device):
+        return None
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != 256 or not bias.is_contiguous()
+                             or bias.data_ptr() % 16 or bias.device != X.device):
+        return None
+    Y = torch.empty((X.shape[0], 256), dtype=torch.float32, device=X.device)
+    if X.shape[0] == 0:
+        return Y
+    _native.launch("gcn_gemm_xw256_f32_b3_logsoftmax", X.device, X.data_ptr(), X.stride(0), W.data_ptr(),
+                   W.stride(0), bias.detach().data_ptr() if bias is not None else None, Y.data_ptr(), Y.stride(0),
+                   X.shape[0], workspace=_native.lib().gcn_gemm_xw256_b3_workspace_bytes())
+    return Y
+
+
 def gemm_bf16(X, W, bias=None, relu=False, dropout_p=0.0, seed=0, row_base=0, mask_src=None,
               mask_rows=None, mask_scale=1.0):
     """X[M,K] · W[K,N] for bf16 storage through the streaming MFMA kernel (C-ABI gcn_gemm_xw_bf16;

@@ -44,9 +44,74 @@ def set_timing_records(records):
     _timing_records = records
 
 
-def spmm_csr(graph, B, bias=None, relu=False, out=None, tag="fwd", dropout_p=0.0, seed=0,
+class PackedRows:
+    """A 256-wide fp32 matrix as fixed 512-byte slots (rows_pack512) next to the matrix itself: `slots` int32
+    [m, 128] — per row four 128-byte sub-slots, one per column quarter (64-bit mask, count, non-zero values in
+    bit order; include/gcn_spmm.h) — and `dense`, read by a gather only for rows a quarter of which did not fit."""
+    __slots__ = ("slots", "dense")
+
+    def __init__(self, slots, dense):
+        self.slots, self.dense = slots, dense
+
+
+PACK512_CAPACITY = 29      # values per sub-slot (GCN_PACK512_CAPACITY)
+
+
+def rows_pack512_usable(h):
+    """Can rows_pack512 take `h` as it is (fp32 [m, 256], unit column stride, 16-byte aligned rows)?"""
+    return (h.is_cuda and h.dim() == 2 and h.dtype == torch.float32 and h.shape[1] == 256 and h.stride(1) == 1
+            and h.stride(0) % 4 == 0 and h.data_ptr() % 16 == 0)
+
+
+def rows_pack512(h):
+    """PackedRows of `h` (C-ABI gcn_rows_pack512: one streaming pass, 1 KiB read and at most 512 bytes written
+    per row) — the operand form of spmm_csr(graph, packed=...) for a mostly-zero activation such as the
+    ReLU + dropout output that layer 2 gathers."""
+    _require_cuda(h, "h")
+    if not rows_pack512_usable(h):
+        raise RuntimeError(f"rows_pack512: {tuple(h.shape)} {h.dtype}: fp32 [m, 256] with 16-byte aligned rows")
+    slots = torch.empty((h.shape[0], 128), dtype=torch.int32, device=h.device)
+    if h.shape[0]:
+        _native.launch("gcn_rows_pack512", h.device, h.data_ptr(), h.stride(0), h.shape[0], slots.data_ptr())
+    return PackedRows(slots, h)
+
+
+def _spmm_csr_packed(graph, packed, out, tag):
+    """spmm_csr's launch for a PackedRows operand (C-ABI gcn_spmm_csr_packed): plain product, bit-identical to
+    the dense launch on packed.dense."""
+    if not isinstance(graph, CSRGraph) or not isinstance(packed, PackedRows):
+        raise RuntimeError("spmm_csr: graph must be a CSRGraph and packed a PackedRows")
+    B, slots = packed.dense, packed.slots
+    if B.shape[0] != graph.shape[1] or B.device != graph.device or not rows_pack512_usable(B) \
+            or tuple(slots.shape) != (B.shape[0], 128) or not slots.is_contiguous():
+        raise RuntimeError(f"size mismatch, adj {graph.shape} x packed {tuple(B.shape)}")
+    n_rows = graph.shape[0]
+    if out is None:
+        out = torch.empty((n_rows, 256), dtype=torch.float32, device=B.device)
+    elif out.shape != (n_rows, 256) or out.dtype != torch.float32 or out.stride(1) != 1:
+        raise RuntimeError("spmm_csr: bad `out`")
+    if n_rows == 0:
+        return out
+    L = _native.lib()
+    plan = graph.plan(torch.float32)
+    ws_bytes = L.gcn_spmm_workspace_bytes(plan, 256)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=B.device) if ws_bytes else None
+    with torch.cuda.device(B.device):
+        rec = _timing_records
+        if rec is not None:
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+        _native.launch("gcn_spmm_csr_packed", B.device, plan, slots.data_ptr(), B.data_ptr(), B.stride(0),
+                       out.data_ptr(), out.stride(0), ws.data_ptr() if ws is not None else None, ws_bytes)
+        if rec is not None:
+            ev1.record()
+            rec.append((tag, ev0, ev1, graph))
+    return out
+
+
+def spmm_csr(graph, B=None, bias=None, relu=False, out=None, tag="fwd", dropout_p=0.0, seed=0,
              b_hint=None, B2=None, c_flags=None, log_softmax=False, c_select=None,
-             skip_zero_rows=False, row_base=0, c_absmax=None):
+             skip_zero_rows=False, row_base=0, c_absmax=None, packed=None):
     """C = A · B (+ bias, ReLU, inverted dropout) on the current HIP stream; A is a CSRGraph,
     B dense [n_cols, F].  The epilogue order is that of the reference model: bias
     (layers.py:35-36), F.relu (models.py:48), F.dropout (models.py:50).  `b_hint` = (row bitmap
@@ -68,7 +133,14 @@ def spmm_csr(graph, B, bias=None, relu=False, out=None, tag="fwd", dropout_p=0.0
     index of its first row and draws the masks of the single-GPU run.
     `c_absmax`: optional DEVICE float32 [1], zeroed by the caller: receives max|stored value| of the
     launch (gcn_epilogue.c_absmax) — the bound a scaled GEMM consuming the result needs, without a
-    reduction pass; non-finite if the result holds inf / NaN."""
+    reduction pass; non-finite if the result holds inf / NaN.
+    `packed` (a PackedRows, INSTEAD of B): the operand's rows are gathered from their 512-byte slots — the same
+    products in the same order, bit-identical to the launch on packed.dense; plain product only."""
+    if packed is not None:
+        if (B is not None or bias is not None or relu or dropout_p or b_hint is not None or B2 is not None
+                or c_flags is not None or log_softmax or c_select is not None or c_absmax is not None):
+            raise RuntimeError("spmm_csr: a packed operand takes the plain product only")
+        return _spmm_csr_packed(graph, packed, out, tag)
     if not isinstance(graph, CSRGraph):
         raise RuntimeError("spmm_csr: graph must be a CSRGraph")
     _require_cuda(B, "dense operand")
