@@ -35,15 +35,26 @@ for validation on other rows, as upstream's --fastmode does.  Opt-in, `restrict_
 on R, layer 1 on R2, compact activations, the dropout mask of the full pass (spmm.dropout_rows) — and
 the full matrix never exists.
 
-The backward pass is written ONCE, as two stages every route drives — `_loss_rows_stage` (grad_pre2
-and grad_b2) and `_hidden_layer_stage` (grad_W2, grad_pre1, grad_b1, grad_W1 from the saved Â·X) —
-with the route's own sparse product between them: `_gcn2_backward_rows` (the block of Âᵀ),
-`_gcn2_backward_dense` (the full CSR(Âᵀ), no row lists), the sharded pass of
-pygcn_amd/sharded_fused.py (the block plus a halo of gradient rows), and, for the first stage, the
-last-layer branch of `GraphConvFunction._backward_rows` (pygcn_amd/spmm.py).
+Each pass is written ONCE; the three autograd nodes (GCN2RowsFunction, GCN2Function,
+GCN2RestrictedFunction) only name their route:
+
+  * `_gcn2_forward(..., rs=None)`: the full pass, or with `rs` the restricted one; what the two do
+    differently is listed in its docstring and nowhere else.  It leaves `ctx.fw`, ONE record of what
+    the backward pass reads (scale, x_bound, z_bound, h_bound, reassoc, keep_bits, bias_dtypes).
+  * `_gcn2_backward(..., rs=None, restricted=False)`: loss rows (`_loss_rows_stage`: grad_pre2,
+    grad_b2) -> early return -> the layer-2 transpose product -> hidden layer (`_hidden_layer_stage`:
+    grad_W2, grad_pre1, grad_b1, grad_W1 from the saved Â·X) -> layer-1 tail; the routes — rows, dense,
+    restricted — differ in the operands its docstring tabulates.  `_gcn2_backward_rows` and
+    `_gcn2_backward_dense` are the first two by name (GCN2Function.backward picks between them).
+  * `input_product(graph, x, rs=None)`: the one cache of Â·X (and of Â[R2,:]·X).
+
+The two stages have two more callers: the sharded pass of pygcn_amd/sharded_fused.py (the block plus a
+halo of gradient rows between them; it fills the same record) and, for the first stage, the last-layer
+branch of `GraphConvFunction._backward_rows` (pygcn_amd/spmm.py).
 """
 import os
 import weakref
+from types import SimpleNamespace
 
 import torch
 
@@ -108,7 +119,7 @@ class RowSets:
         self.hint2 = pack_row_flags(mask2)
 
     _restricted = None       # (graph.val version, a_rows2, a_block), built by restricted()
-    _input_product = None    # (weakref of X, its version, graph.val version, a_rows2·X): restricted_input_product
+    _input_product = None    # (weakref of X, its version, graph.val version, a_rows2·X): input_product(.., rs)
 
     def restricted(self, graph):
         """The two row blocks of Â the RESTRICTED forward pass multiplies with (GCN2RestrictedFunction),
@@ -185,16 +196,19 @@ def set_input_product_cache(enabled):
     _CACHE_INPUT_PRODUCT = bool(enabled)
 
 
-def input_product(graph, x):
-    """z = Â·X for the layer-1 input, from the per-graph cache when set_input_product_cache(True)
-    and neither the graph's values nor X changed since it was computed."""
+def input_product(graph, x, rs=None):
+    """z = Â·X for the layer-1 input, from the per-graph cache when set_input_product_cache(True), X
+    needs no gradient, and neither the graph's values nor X changed since it was computed.  With `rs`:
+    z_c = Â[R2, :]·X, the compact input of the restricted pass, under the same rule; that product
+    hangs on the row sets (`rs._input_product`) where the full one hangs on the graph."""
+    a, holder = (graph, graph) if rs is None else (rs.restricted(graph)[0], rs)
     if not _CACHE_INPUT_PRODUCT or x.requires_grad:
-        return spmm_csr(graph, x)
-    hit = getattr(graph, "_input_product", None)
+        return spmm_csr(a, x)
+    hit = getattr(holder, "_input_product", None)
     if (hit is not None and hit[0]() is x and hit[1] == x._version and hit[2] == graph.val._version):
         return hit[3]
-    z = spmm_csr(graph, x)
-    graph._input_product = (weakref.ref(x), x._version, graph.val._version, z)
+    z = spmm_csr(a, x)
+    holder._input_product = (weakref.ref(x), x._version, graph.val._version, z)
     return z
 
 
@@ -236,16 +250,58 @@ def _layer2_packed(graph, h1, w2, b2):
     return _gemm.gemm_xw256_log_softmax(z2, w2, b2)
 
 
-def _gcn2_forward(ctx, x, w1, b1, w2, b2, graph, dropout_p, seed):
-    """Forward pass shared by the one-node functions: (tensor saved in place of x, h1, logp).
-    Fills ctx.scale / x_bound / z_bound / h_bound / reassoc / has_bias / bias_dtypes."""
+def _forward_record(dropout_p, b1, b2):
+    """`ctx.fw`: everything a one-node forward pass leaves for its backward pass besides the saved
+    tensors (the sharded pass of pygcn_amd/sharded_fused.py fills the same record):
+        scale                      1 / (1 - p) of the dropout
+        x_bound, z_bound, h_bound  bounds of max|X|, max|Â·X|, max|h1| for the scaled GEMMs ("h2"), else None
+        reassoc                    layer 1 ran as (Â·X)·W1: the tensor saved in place of X is z = Â·X
+        keep_bits                  `h1 > 0` as one bit per element where the layer GEMM wrote it, else None
+        bias_dtypes                (b1's, b2's) dtype, None for a layer without bias"""
+    return SimpleNamespace(scale=_spmm.dropout_scale(dropout_p), x_bound=None, z_bound=None, h_bound=None,
+                           reassoc=False, keep_bits=None,
+                           bias_dtypes=(b1.dtype if b1 is not None else None, b2.dtype if b2 is not None else None))
+
+
+def _gcn2_forward(ctx, x, w1, b1, w2, b2, graph, dropout_p, seed, rs=None):
+    """Forward pass of every one-node function: (tensor saved in place of x, h1, logp).  Leaves ctx.graph
+    and the record ctx.fw (_forward_record).
+
+    With `rs` (the row sets of the loss rows: GCN2RestrictedFunction) the pass is RESTRICTED to their
+    receptive field — layer 2 on the rows R reads h1 on R2, layer 1 on R2 reads X everywhere; h1 is
+    compact [n2, H], logp is [n_u, C] in the order of rs.rows_u — the same sums for the rows it keeps:
+
+        reassociated layer 1     z_c = Â[R2,:]·X      h1_c = relu(z_c·W1 + b1)        GEMM on n2 rows
+        other widths             sup1 = X·W1 [N, H]   h1_c = relu(Â[R2,:]·sup1 + b1)
+        dropout_rows(h1_c, R2)   the keep bits of the full pass at rows R2 (in place)
+        sup2_c = h1_c·W2         logp_u = log_softmax(Â[R,R2]·sup2_c + b2)
+
+    The two passes differ in this and nothing else (some of it decides result bits under "h2"):
+
+                                   full pass                               restricted pass
+        layer-1 matrix `a1`, and   graph                                   Â[R2,:] = rs.restricted(graph)[0]
+        its inf_norm() in z_bound
+        / h_bound
+        the cached Â·X hangs on    graph._input_product                    rs._input_product
+        dropout                    in the store of the layer_gemm / SpMM   not in the launch: dropout_rows(h1,
+                                   launch (`in_launch`)                    rs.rows2, p, seed) after it
+        h_bound, reassociated      the maximum the GEMM reports, as it is  that maximum x 1.0001·scale (dropout
+        path                                                               follows the launch)
+        keep bits                  where gemm_keep_bits_usable and a       never (the mask is h1_c > 0)
+                                   gradient is needed
+        layer 2, matrix `a2`       the packed route where                  spmm_csr(Â[R,R2], h1·W2, log_softmax)
+                                   packed_hidden_applies, else
+                                   spmm_csr(graph, h1·W2, log_softmax)"""
+    restricted = rs is not None
+    a1, a2 = rs.restricted(graph) if restricted else (graph, graph)
+    in_launch = {} if restricted else {"dropout_p": dropout_p, "seed": seed}
     ctx.graph = graph
-    ctx.scale = _spmm.dropout_scale(dropout_p)
+    fw = ctx.fw = _forward_record(dropout_p, b1, b2)
     # bounds of max|operand| for the scaled fp16 GEMMs (set_gemm_scheme("h2") only; the default
     # three-part bf16 GEMMs need none), without a pass over the data:
     # X is constant (cached), and |Â·B| <= ‖Â‖∞·max|B|
     bounded = x.dtype == torch.float32 and _gemm.gemm_needs_bounds()
-    ctx.x_bound = _gemm.absmax_cached(x) if bounded else None
+    fw.x_bound = _gemm.absmax_cached(x) if bounded else None
     # Layer 1 REASSOCIATED when a GEMM kernel can carry the layer's epilogue (256 -> 256 fp32;
     # bf16 128 -> 128 / 256):
     #     h1 = dropout(relu((Â·X)·W1 + b1))        instead of   dropout(relu(Â·(X·W1) + b1))
@@ -253,40 +309,40 @@ def _gcn2_forward(ctx, x, w1, b1, w2, b2, graph, dropout_p, seed):
     # width, a GEMM), but the product z = Â·X of THIS forward pass is then all the backward
     # pass needs for grad_W1 = zᵀ·grad_pre1: no second sparse product for layer 1 (12.7 ms at
     # C4, 35.5 ms at C5).
-    ctx.reassoc = bool(_gemm.layer_gemm_reassociable(x, w1, b1))
-    ctx.keep_bits = None
+    fw.reassoc = bool(_gemm.layer_gemm_reassociable(x, w1, b1))
     h1 = h_bound = z = None
-    ctx.z_bound = None
-    if ctx.reassoc:
-        z = input_product(graph, x)
+    if fw.reassoc:
+        z = input_product(graph, x, rs)
         if bounded:
-            ctx.z_bound = graph.inf_norm() * ctx.x_bound * 1.0001
-            h_bound = torch.zeros(1, dtype=torch.float32, device=x.device)   # max|h1|, exact
+            fw.z_bound = a1.inf_norm() * fw.x_bound * 1.0001
+            h_bound = torch.zeros(1, dtype=torch.float32, device=x.device)   # max|h1| of the launch, exact
         # `h1 > 0` — all the backward of ReLU / dropout asks of h1 — as one bit per element, written by the
         # same launch where it can: the masked grad_input GEMM then reads 32 bytes per row instead of 1 KiB
-        if _gemm.gemm_keep_bits_usable(z, None, dropout_p) and any(ctx.needs_input_grad):
-            ctx.keep_bits = torch.empty((z.shape[0], 8), dtype=torch.int32, device=z.device)
-        h1 = _gemm.layer_gemm(z, w1, ctx.z_bound, h_bound, bias=b1, relu=True, dropout_p=dropout_p,
-                              seed=seed, keep_bits_out=ctx.keep_bits)
+        if not restricted and _gemm.gemm_keep_bits_usable(z, None, dropout_p) and any(ctx.needs_input_grad):
+            fw.keep_bits = torch.empty((z.shape[0], 8), dtype=torch.int32, device=z.device)
+        h1 = _gemm.layer_gemm(z, w1, fw.z_bound, h_bound, bias=b1, relu=True, keep_bits_out=fw.keep_bits, **in_launch)
         if h1 is None:                     # (alignment the kernel cannot take)
-            ctx.reassoc, z, h_bound, ctx.keep_bits = False, None, None, None
+            fw.reassoc, z, h_bound, fw.keep_bits = False, None, None, None
+        elif bounded and restricted:
+            h_bound = h_bound * (1.0001 * fw.scale)
     if h1 is None:
         s_max = torch.zeros(1, dtype=torch.float32, device=x.device) if bounded else None
-        sup1 = _dense_forward(x, w1, ctx.x_bound, s_max)
-        h1 = spmm_csr(graph, sup1, bias=b1, relu=True, dropout_p=dropout_p, seed=seed)
+        sup1 = _dense_forward(x, w1, fw.x_bound, s_max)
+        h1 = spmm_csr(a1, sup1, bias=b1, relu=True, **in_launch)
         del sup1
         if bounded:   # |relu/dropout(Â·S + b)| <= (‖Â‖∞·max|S| + max|b|) / (1 - p)
-            h_bound = graph.inf_norm() * s_max
+            h_bound = a1.inf_norm() * s_max
             if b1 is not None:
                 h_bound = h_bound + b1.detach().abs().max().float()
-            h_bound = h_bound * (1.0001 * ctx.scale)
-    ctx.h_bound = h_bound
-    logp = _layer2_packed(graph, h1, w2, b2) if packed_hidden_applies(h1, w2, b2, dropout_p) else None
+            h_bound = h_bound * (1.0001 * fw.scale)
+    if restricted and dropout_p > 0.0:
+        _spmm.dropout_rows(h1, rs.rows2, dropout_p, seed)
+    fw.h_bound = h_bound
+    logp = _layer2_packed(graph, h1, w2, b2) if (not restricted and packed_hidden_applies(h1, w2, b2, dropout_p)) \
+        else None
     if logp is None:
-        logp = spmm_csr(graph, _dense_forward(h1, w2, h_bound), bias=b2, log_softmax=True)
-    ctx.has_bias = (b1 is not None, b2 is not None)
-    ctx.bias_dtypes = (b1.dtype if b1 is not None else None, b2.dtype if b2 is not None else None)
-    return (z if ctx.reassoc else x), h1, logp
+        logp = spmm_csr(a2, _dense_forward(h1, w2, h_bound), bias=b2, log_softmax=True)
+    return (z if fw.reassoc else x), h1, logp
 
 
 def _loss_rows_stage(grad, logp, want_colsum, rs=None, round_first=False):
@@ -328,10 +384,9 @@ def _loss_rows_stage(grad, logp, want_colsum, rs=None, round_first=False):
     return gp, colsum
 
 
-def _hidden_layer_stage(h1, w2, grad_sup2, gs_bound, z, need_w2, need_w1, b1_dtype, scale, h_bound,
-                        z_bound, keep_bits, rows=None, l1_follows_l2=False):
-    """HIDDEN LAYER, the stage after the route's own layer-2 sparse product: from grad_sup2 (and
-    `gs_bound`, its bound for the scaled GEMMs, or None)
+def _hidden_layer_stage(fw, h1, w2, grad_sup2, gs_bound, z, needs, rows=None, l1_follows_l2=False):
+    """HIDDEN LAYER, the stage after the route's own layer-2 sparse product: from the forward pass's
+    record `fw` (_gcn2_forward), grad_sup2 (and `gs_bound`, its bound for the scaled GEMMs, or None)
 
         grad_W2   = h1ᵀ · grad_sup2         gather-fused MFMA kernel (weight_grad_rows)
         grad_pre1 = mask(grad_sup2 · W2ᵀ)   MFMA GEMM with the ReLU / dropout mask (h1 > 0, or its
@@ -344,8 +399,9 @@ def _hidden_layer_stage(h1, w2, grad_sup2, gs_bound, z, need_w2, need_w1, b1_dty
     [n2, ·], and h1 / z are read in place through the lists — or None = all rows, in order (the
     convention of weight_grad_rows' `rows_a` and gemm_xw256's `mask_rows`, which receive it as it
     is).  `z` = Â·X saved by a reassociated first layer, or None: grad_W1 is then the caller's.
-    `b1_dtype`: dtype of the bias gradient, None when it is not wanted.  Shapes a kernel declines
-    fall through to the next form (each returns None before it allocates or launches).
+    `needs` = (need_w1, need_b1, need_w2); grad_b1 comes in the bias's dtype, fw.bias_dtypes[0].
+    Shapes a kernel declines fall through to the next form (each returns None before it allocates
+    or launches).
     `l1_follows_l2`: the full-height and the sharded pass reach for layer 1's gather-fused fp32
     kernels only where layer 2's GEMMs were on theirs (256 classes too); the single-GPU row pass
     asks the kernels alone.  The routes differ there (256 -> 256 -> C < 256), and each keeps its
@@ -353,6 +409,9 @@ def _hidden_layer_stage(h1, w2, grad_sup2, gs_bound, z, need_w2, need_w1, b1_dty
     Returns (grad_pre1, its bound or None, grad_W2, grad_b1, grad_W1)."""
     dev, dt = h1.device, h1.dtype
     f32 = dt == torch.float32
+    need_w1, need_b1, need_w2 = needs
+    b1_dtype = fw.bias_dtypes[0] if need_b1 else None
+    scale, h_bound, z_bound, keep_bits = fw.scale, fw.h_bound, fw.z_bound, fw.keep_bits
     rows2, rows2_i32, rows2_padded, n2 = (rows.rows2, rows.rows2_i32, rows.rows2_padded, rows.n2) \
         if rows is not None else (None,) * 4
     if n2 == 0:          # an empty list (a rank without labelled neighbourhood): every sum is empty
@@ -405,110 +464,108 @@ def _hidden_layer_stage(h1, w2, grad_sup2, gs_bound, z, need_w2, need_w1, b1_dty
     return gpre1, gh_max, grad_w2, grad_b1, grad_w1
 
 
-def _gcn2_backward_rows(ctx, x, w1, w2, h1, out_rows, rs, grad_rows, needs):
-    """Backward pass for a gradient that is non-zero on the loss rows only (module docstring):
-    `grad_rows` [|rows|, C] in the user's row order, `out_rows` = logp at those rows.
-    Returns (grad_x, grad_w1, grad_b1, grad_w2, grad_b2)."""
-    graph = ctx.graph
+def _gcn2_backward(ctx, x, w1, w2, h1, logp, grad, needs, rs=None, restricted=False):
+    """The backward pass of every single-GPU one-node function, in five steps: loss rows, early return,
+    the layer-2 transpose product, hidden layer, layer-1 tail.  `grad` is the gradient that arrives for
+    `logp` (for the routes with row sets `rs`: [|rows|, C] in the user's row order, `logp` = the
+    log-probabilities at those rows); `x` is the z = Â·X the forward pass saved when ctx.fw.reassoc.
+    Returns (grad_x, grad_w1, grad_b1, grad_w2, grad_b2).  The routes differ in this and nothing else:
+
+                                   rows (rs)                 dense (no rs)            restricted (rs, restricted)
+        h1 / z / x saved by        full height, read in      full height              COMPACT [n2, ·]: "all rows, in
+        the forward pass           place through rs's lists                           order" of their own height
+        loss stage                 rs                        no row sets              rs
+        layer-2 operand            rs.at_block               CSR(Âᵀ)                  rs.at_block
+        hidden stage `rows=`       rs                        None                     None (rs when R2 is empty:
+                                                                                      the stage returns the zeros)
+        `l1_follows_l2`            no                        yes                      no
+        layer-1 matrix             CSR(Âᵀ)                   CSR(Âᵀ)                  Â[R2,:]ᵀ
+        its operand                compact -> [N, ·] by      as it is                 as it is
+                                   _operand_buffer, b_hint
+        grad_W1 from a forward     yes (c_select; no grad_x  no                       no
+        product on rows R2         and Fin <= 2·H)
+        empty R2                   the hidden stage's zeros  —                        zero grad_x / grad_W1 here
+
+    Nothing of size [N, ·] exists on the rows route before the layer-1 operand; the dense route is the
+    minimum number of full-height sweeps, each stage handing the next what it needs; none synchronises
+    with the host."""
+    fw, graph = ctx.fw, ctx.graph
     need_x, need_w1, need_b1, need_w2, need_b2 = needs
-    n, dev, dt = graph.shape[0], x.device, h1.dtype
-    graph_t = graph.t()
-    # ---- loss rows, compact [|R|, C]
-    gp, colsum = _loss_rows_stage(grad_rows, out_rows, ctx.has_bias[1] and need_b2, rs)
-    grad_b2 = colsum.to(ctx.bias_dtypes[1]) if colsum is not None else None
+    dev, dt = h1.device, h1.dtype
+    f32 = dt == torch.float32
+    listed = rs is not None and not restricted           # the rows route
+    a1_t = None if restricted else graph.t()             # (restricted: Â[R2,:]ᵀ, built where the tail needs it)
+    # ---- loss rows ([|R|, C] with row sets); for the mean-NLL gradient over all rows (NLLGrad,
+    # pygcn_amd/functional.py) the loss gradient is never materialised
+    gp, colsum = _loss_rows_stage(grad, logp, fw.bias_dtypes[1] is not None and need_b2, rs)
+    grad_b2 = colsum.to(fw.bias_dtypes[1]) if colsum is not None else None
     grad_w1 = grad_w2 = grad_b1 = grad_x = None
     if not (need_x or need_w1 or need_b1 or need_w2):
         return grad_x, grad_w1, grad_b1, grad_w2, grad_b2
-    # ---- layer 2: Âᵀ · grad_pre2 — only rows R of grad_pre2 are non-zero and only rows R2 of
-    # the result can be: the product runs on that block of Âᵀ (RowSets.at_block), compact
-    # operand [|R|, C] in, compact result [|R2|, C] out; nothing of size [N, C] exists
-    f32 = dt == torch.float32
-    # bound of max|grad_sup2| for the scaled GEMMs: its EXACT maximum, reported by the product
-    # itself (gcn_epilogue.c_absmax: one conditional atomic per wave) — ‖Âᵀ‖∞·max|grad_pre2| would
-    # overshoot by the hub column sums, a separate reduction pass costs 0.5 ms at C4
+    # ---- layer 2: Âᵀ · grad_pre2.  With row sets only rows R of grad_pre2 are non-zero and only rows
+    # R2 of the result can be: the product runs on that block of Âᵀ (RowSets.at_block), compact operand
+    # [|R|, C] in, compact result [|R2|, C] out.
+    # Bound of max|grad_sup2| for the scaled GEMMs: its EXACT maximum, reported by the product itself
+    # (gcn_epilogue.c_absmax: one conditional atomic per wave) — ‖Âᵀ‖∞·max|grad_pre2| would overshoot
+    # by the hub column sums, a separate reduction pass costs 0.5 ms at C4 (2 ms at full height)
     gs_max = torch.zeros(1, dtype=torch.float32, device=dev) if f32 else None
-    grad_sup2 = spmm_csr(rs.at_block, gp.contiguous(), tag="bwd_l2", c_absmax=gs_max)
+    grad_sup2 = spmm_csr(rs.at_block if rs is not None else a1_t, gp.contiguous(), tag="bwd_l2", c_absmax=gs_max)
+    del gp
     gs_bound = gs_max * 1.0001 if f32 else None
-    # ---- hidden layer, on the rows R2 (h1 and z read in place through the row lists)
+    # ---- hidden layer
     gpre1, gpre_bound, grad_w2, grad_b1, grad_w1 = _hidden_layer_stage(
-        h1, w2, grad_sup2, gs_bound, x if ctx.reassoc else None, need_w2, need_w1,
-        ctx.bias_dtypes[0] if (ctx.has_bias[0] and need_b1) else None,
-        ctx.scale, ctx.h_bound, ctx.z_bound, ctx.keep_bits, rows=rs)
+        fw, h1, w2, grad_sup2, gs_bound, x if fw.reassoc else None, (need_w1, need_b1, need_w2),
+        rows=rs if (listed or (restricted and rs.n2 == 0)) else None, l1_follows_l2=rs is None)
     del grad_sup2
-    # ---- layer 1
-    if ctx.reassoc:                                     # (x is this step's Â·X, saved by forward)
-        if need_x:                                      # grad_X = Âᵀ·(grad_pre1·W1ᵀ)
-            gz = _dense_forward(gpre1, w1.t().contiguous(), gpre_bound)
-            grad_z = _operand_buffer(n, gz.shape[1], dt, dev, rs.rows2, gz, rs.n2)
-            grad_x = spmm_csr(graph_t, grad_z, tag="bwd_l1", b_hint=rs.hint2)
-    elif not need_x and x.shape[1] <= _spmm.REASSOC_MAX_WIDTH_RATIO * gpre1.shape[1]:
+    # ---- layer 1 (reassociated: grad_W1 is done, and x is this step's Â·X)
+    if restricted and rs.n2 == 0:                        # (no vertex feeds the loss rows: every sum is empty)
+        if need_x:
+            grad_x = torch.zeros((graph.shape[1], w1.shape[0]), dtype=dt, device=dev)
+        if need_w1 and grad_w1 is None:
+            grad_w1 = torch.zeros_like(w1)
+    elif listed and not fw.reassoc and not need_x and x.shape[1] <= _spmm.REASSOC_MAX_WIDTH_RATIO * gpre1.shape[1]:
         if need_w1:
             # grad_W1 = (Â·X)[R2]ᵀ · grad_pre1[R2]: a forward product restricted to rows R2
+            n = graph.shape[0]
             z = spmm_csr(graph, x, tag="bwd_l1", c_select=rs.hint2[0],
                          out=_spmm._maybe_poisoned((n, x.shape[1]), x.dtype, dev))
             if f32 and _gemm.gemm_handwritten() and x.shape[1] == 256 and gpre1.shape[1] == 256:
-                z_bound = graph.inf_norm() * ctx.x_bound * 1.0001 if ctx.x_bound is not None else None
+                z_bound = graph.inf_norm() * fw.x_bound * 1.0001 if fw.x_bound is not None else None
                 grad_w1 = _gemm.weight_grad_rows(z, gpre1, rs.rows2_padded, None, z_bound,
                                                  gpre_bound, n_list=rs.n2)
             if grad_w1 is None:
                 grad_w1 = _weight_grad(z.index_select(0, rs.rows2), gpre1)
-    elif need_x or need_w1:
-        grad_pre1 = _operand_buffer(n, gpre1.shape[1], dt, dev, rs.rows2, gpre1, rs.n2)
-        grad_sup1 = spmm_csr(graph_t, grad_pre1, tag="bwd_l1", b_hint=rs.hint2)
-        if need_w1:
-            grad_w1 = _weight_grad(x, grad_sup1)
-        if need_x:
-            grad_x = _dense_forward(grad_sup1, w1.t().contiguous())
+    elif need_x or (need_w1 and not fw.reassoc):
+        # ONE transpose product: of grad_pre1·W1ᵀ when layer 1 was reassociated (its result is grad_X),
+        # else of grad_pre1 (grad_sup1, which grad_W1 = Xᵀ·grad_sup1 and grad_X = grad_sup1·W1ᵀ share)
+        if restricted:
+            a1_t = rs.restricted(graph)[0].t()
+        g1 = _dense_forward(gpre1, w1.t().contiguous(), gpre_bound) if fw.reassoc else gpre1
+        if listed:
+            g1 = _operand_buffer(graph.shape[0], g1.shape[1], dt, dev, rs.rows2, g1, rs.n2)
+        elif not fw.reassoc:
+            g1 = g1.contiguous()
+        g1 = spmm_csr(a1_t, g1, tag="bwd_l1", b_hint=rs.hint2 if listed else None)
+        if fw.reassoc:
+            grad_x = g1
+        else:
+            if need_w1:
+                grad_w1 = _weight_grad(x, g1)
+            if need_x:
+                grad_x = _dense_forward(g1, w1.t().contiguous())
     return grad_x, grad_w1, grad_b1, grad_w2, grad_b2
+
+
+def _gcn2_backward_rows(ctx, x, w1, w2, h1, out_rows, rs, grad_rows, needs):
+    """The rows route of _gcn2_backward: a gradient that is non-zero on the loss rows only (module
+    docstring), after a full-height forward pass."""
+    return _gcn2_backward(ctx, x, w1, w2, h1, out_rows, grad_rows, needs, rs)
 
 
 def _gcn2_backward_dense(ctx, x, w1, w2, h1, logp, grad, needs):
-    """Backward pass for a gradient that is non-zero on EVERY row (a loss over all vertices —
-    the fork's live case reduces over all nodes, reference pygcn/train.py:151-155): nothing can be
-    skipped, so the pass is the minimum number of full-height sweeps, each stage handing the next
-    what it needs — no host synchronisation, no search for zero rows:
-
-        grad_pre2 (+ grad_b2)   _loss_rows_stage over all rows; for the mean-NLL gradient (NLLGrad,
-                                pygcn_amd/functional.py) the loss gradient is never materialised:
-                                coef·(onehot(target) − exp(logp)) straight from logp and the labels
-        grad_sup2 = Âᵀ·grad_pre2        the SpMM kernel on CSR(Âᵀ), full height
-        grad_W2, grad_pre1, grad_b1     _hidden_layer_stage without row lists (all rows, in order)
-        grad_W1   = zᵀ·grad_pre1        there too, with z = Â·X of the forward pass (layer 1
-                                        reassociated); other shapes: Âᵀ·grad_pre1 first
-    Returns (grad_x, grad_w1, grad_b1, grad_w2, grad_b2)."""
-    graph = ctx.graph
-    need_x, need_w1, need_b1, need_w2, need_b2 = needs
-    dev, f32 = x.device, h1.dtype == torch.float32
-    graph_t = graph.t()
-    gp, colsum = _loss_rows_stage(grad, logp, ctx.has_bias[1] and need_b2)
-    grad_b2 = colsum.to(ctx.bias_dtypes[1]) if colsum is not None else None
-    del grad
-    grad_w1 = grad_w2 = grad_b1 = grad_x = None
-    if not (need_x or need_w1 or need_b1 or need_w2):
-        return grad_x, grad_w1, grad_b1, grad_w2, grad_b2
-    # exact max|grad_sup2| from the product itself (gcn_epilogue.c_absmax); the analytic
-    # ‖Âᵀ‖∞·max|g| is loose by the hub column sums and would cost the scaled GEMMs their low-order
-    # bits, a separate reduction over [10⁷, 256] costs 2 ms
-    gs_max = torch.zeros(1, dtype=torch.float32, device=dev) if f32 else None
-    grad_sup2 = spmm_csr(graph_t, gp.contiguous(), tag="bwd_l2", c_absmax=gs_max)
-    del gp
-    gs_bound = gs_max * 1.0001 if f32 else None
-    gpre1, gpre_bound, grad_w2, grad_b1, grad_w1 = _hidden_layer_stage(
-        h1, w2, grad_sup2, gs_bound, x if ctx.reassoc else None, need_w2, need_w1,
-        ctx.bias_dtypes[0] if (ctx.has_bias[0] and need_b1) else None,
-        ctx.scale, ctx.h_bound, ctx.z_bound, ctx.keep_bits, l1_follows_l2=True)
-    del grad_sup2
-    if ctx.reassoc:
-        if need_x:
-            gz = _dense_forward(gpre1, w1.t().contiguous(), gpre_bound)
-            grad_x = spmm_csr(graph_t, gz, tag="bwd_l1")
-    elif need_x or need_w1:
-        grad_sup1 = spmm_csr(graph_t, gpre1.contiguous(), tag="bwd_l1")
-        if need_w1:
-            grad_w1 = _weight_grad(x, grad_sup1)
-        if need_x:
-            grad_x = _dense_forward(grad_sup1, w1.t().contiguous())
-    return grad_x, grad_w1, grad_b1, grad_w2, grad_b2
+    """The dense route of _gcn2_backward: a gradient that is non-zero on EVERY row (a loss over all
+    vertices — the fork's live case reduces over all nodes, reference pygcn/train.py:151-155)."""
+    return _gcn2_backward(ctx, x, w1, w2, h1, logp, grad, needs)
 
 
 class GCN2RowsFunction(torch.autograd.Function):
@@ -541,9 +598,8 @@ class GCN2Function(torch.autograd.Function):
     the gradient that arrives:
 
       * a `RowGrad` (the caller selected `output[idx_train]`, pygcn/train.py:153 — pygcn_amd/rowgrad.py):
-        the row-restricted pass of the module docstring, on the cached row sets of (graph, idx);
-      * an `NLLGrad` (pygcn_amd.functional.nll_loss over all rows) or any dense tensor: the
-        full-height pass of `_gcn2_backward_dense`.
+        the rows route, on the cached row sets of (graph, idx);
+      * an `NLLGrad` (pygcn_amd.functional.nll_loss over all rows) or any dense tensor: the dense route.
     Neither synchronises with the host."""
 
     @staticmethod
@@ -568,108 +624,6 @@ class GCN2Function(torch.autograd.Function):
         return (*grads, None, None, None)
 
 
-def restricted_input_product(rs, graph, a_rows2, x):
-    """z_c = Â[R2, :]·X, the compact layer-1 input of the restricted pass — from the row sets' cache
-    under input_product's rules: set_input_product_cache(True), X needs no gradient, and neither X nor
-    the graph's values changed since it was computed."""
-    if not _CACHE_INPUT_PRODUCT or x.requires_grad:
-        return spmm_csr(a_rows2, x)
-    hit = rs._input_product
-    if (hit is not None and hit[0]() is x and hit[1] == x._version and hit[2] == graph.val._version):
-        return hit[3]
-    z = spmm_csr(a_rows2, x)
-    rs._input_product = (weakref.ref(x), x._version, graph.val._version, z)
-    return z
-
-
-def _gcn2_forward_restricted(ctx, x, w1, b1, w2, b2, graph, rs, dropout_p, seed):
-    """Forward pass on the receptive field of the loss rows only: (tensor saved in place of x, h1_c
-    [n2, H], logp_u [n_u, C] in the order of rs.rows_u).  The sums are those of _gcn2_forward for the
-    rows it keeps — layer 2 on the rows R reads h1 on R2, layer 1 on R2 reads X everywhere:
-
-        reassociated layer 1     z_c = Â[R2,:]·X      h1_c = relu(z_c·W1 + b1)        GEMM on n2 rows
-        other widths             sup1 = X·W1 [N, H]   h1_c = relu(Â[R2,:]·sup1 + b1)
-        dropout_rows(h1_c, R2)   the keep bits of the full pass at rows R2 (in place)
-        sup2_c = h1_c·W2         logp_u = log_softmax(Â[R,R2]·sup2_c + b2)
-
-    Fills the ctx fields _hidden_layer_stage reads, as _gcn2_forward does."""
-    a_rows2, a_block = rs.restricted(graph)
-    ctx.graph = graph
-    ctx.scale = _spmm.dropout_scale(dropout_p)
-    bounded = x.dtype == torch.float32 and _gemm.gemm_needs_bounds()
-    ctx.x_bound = _gemm.absmax_cached(x) if bounded else None
-    ctx.reassoc = bool(_gemm.layer_gemm_reassociable(x, w1, b1))
-    ctx.keep_bits = None         # (the mask is h1_c > 0: dropout is not in the GEMM's store here)
-    ctx.z_bound = None
-    h1 = h_bound = z = None
-    if ctx.reassoc:
-        z = restricted_input_product(rs, graph, a_rows2, x)
-        if bounded:
-            ctx.z_bound = a_rows2.inf_norm() * ctx.x_bound * 1.0001
-            h_bound = torch.zeros(1, dtype=torch.float32, device=x.device)       # max|relu(..)|, exact
-        h1 = _gemm.layer_gemm(z, w1, ctx.z_bound, h_bound, bias=b1, relu=True)
-        if h1 is None:                     # (alignment the kernel cannot take)
-            ctx.reassoc, z, h_bound = False, None, None
-        elif bounded:
-            h_bound = h_bound * (1.0001 * ctx.scale)
-    if h1 is None:
-        s_max = torch.zeros(1, dtype=torch.float32, device=x.device) if bounded else None
-        sup1 = _dense_forward(x, w1, ctx.x_bound, s_max)
-        h1 = spmm_csr(a_rows2, sup1, bias=b1, relu=True)
-        del sup1
-        if bounded:
-            h_bound = a_rows2.inf_norm() * s_max
-            if b1 is not None:
-                h_bound = h_bound + b1.detach().abs().max().float()
-            h_bound = h_bound * (1.0001 * ctx.scale)
-    if dropout_p > 0.0:
-        _spmm.dropout_rows(h1, rs.rows2, dropout_p, seed)
-    ctx.h_bound = h_bound
-    logp_u = spmm_csr(a_block, _dense_forward(h1, w2, h_bound), bias=b2, log_softmax=True)
-    ctx.has_bias = (b1 is not None, b2 is not None)
-    ctx.bias_dtypes = (b1.dtype if b1 is not None else None, b2.dtype if b2 is not None else None)
-    return (z if ctx.reassoc else x), h1, logp_u
-
-
-def _gcn2_backward_restricted(ctx, x, w1, w2, h1, out_rows, rs, grad_rows, needs):
-    """Backward pass of the restricted forward: the stages of _gcn2_backward_rows with the hidden layer
-    on the COMPACT h1_c / z_c — "all rows, in order" of their own height n2, so the contiguous kernels
-    run — and layer 1's transpose product on Â[R2,:]ᵀ.  `x` is z_c when layer 1 was reassociated.
-    Returns (grad_x, grad_w1, grad_b1, grad_w2, grad_b2)."""
-    need_x, need_w1, need_b1, need_w2, need_b2 = needs
-    dev, f32 = h1.device, h1.dtype == torch.float32
-    gp, colsum = _loss_rows_stage(grad_rows, out_rows, ctx.has_bias[1] and need_b2, rs)
-    grad_b2 = colsum.to(ctx.bias_dtypes[1]) if colsum is not None else None
-    grad_w1 = grad_w2 = grad_b1 = grad_x = None
-    if not (need_x or need_w1 or need_b1 or need_w2):
-        return grad_x, grad_w1, grad_b1, grad_w2, grad_b2
-    gs_max = torch.zeros(1, dtype=torch.float32, device=dev) if f32 else None
-    grad_sup2 = spmm_csr(rs.at_block, gp.contiguous(), tag="bwd_l2", c_absmax=gs_max)
-    gs_bound = gs_max * 1.0001 if f32 else None
-    gpre1, gpre_bound, grad_w2, grad_b1, grad_w1 = _hidden_layer_stage(
-        h1, w2, grad_sup2, gs_bound, x if ctx.reassoc else None, need_w2, need_w1,
-        ctx.bias_dtypes[0] if (ctx.has_bias[0] and need_b1) else None,
-        ctx.scale, ctx.h_bound, ctx.z_bound, None, rows=rs if rs.n2 == 0 else None)
-    del grad_sup2
-    if (need_x or (need_w1 and not ctx.reassoc)) and rs.n2:
-        a_rows2_t = rs.restricted(ctx.graph)[0].t()
-        if ctx.reassoc:                                     # grad_X = Â[R2,:]ᵀ·(grad_pre1·W1ᵀ)
-            gz = _dense_forward(gpre1, w1.t().contiguous(), gpre_bound)
-            grad_x = spmm_csr(a_rows2_t, gz, tag="bwd_l1")
-        else:
-            grad_sup1 = spmm_csr(a_rows2_t, gpre1.contiguous(), tag="bwd_l1")
-            if need_w1:
-                grad_w1 = _weight_grad(x, grad_sup1)
-            if need_x:
-                grad_x = _dense_forward(grad_sup1, w1.t().contiguous())
-    elif not rs.n2:                                         # (no vertex feeds the loss rows: every sum is empty)
-        if need_x:
-            grad_x = torch.zeros((ctx.graph.shape[1], w1.shape[0]), dtype=h1.dtype, device=dev)
-        if need_w1 and grad_w1 is None:
-            grad_w1 = torch.zeros_like(w1)
-    return grad_x, grad_w1, grad_b1, grad_w2, grad_b2
-
-
 class GCN2RestrictedFunction(torch.autograd.Function):
     """GCN2RowsFunction's result — log_softmax(Â·dropout(relu(Â·X·W1 + b1))·W2 + b2)[rows] — with the
     FORWARD pass restricted to the receptive field of `rows` too (opt-in: `model(x, adj, rows=idx,
@@ -680,7 +634,7 @@ class GCN2RestrictedFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, graph, rows, dropout_p, seed):
         rs = ctx.rs = row_sets(graph, rows)
-        saved_x, h1, logp_u = _gcn2_forward_restricted(ctx, x, w1, b1, w2, b2, graph, rs, dropout_p, seed)
+        saved_x, h1, logp_u = _gcn2_forward(ctx, x, w1, b1, w2, b2, graph, dropout_p, seed, rs)
         out_rows = logp_u if rs.sorted_unique else logp_u.index_select(0, rs.inverse)
         ctx.save_for_backward(saved_x, w1, w2, h1, out_rows)
         return out_rows
@@ -688,8 +642,8 @@ class GCN2RestrictedFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_rows):
         x, w1, w2, h1, out_rows = ctx.saved_tensors          # (x is z_c = Â[R2,:]·X on the reassociated path)
-        grads = _gcn2_backward_restricted(ctx, x, w1, w2, h1, out_rows, ctx.rs, grad_rows,
-                                          ctx.needs_input_grad[:5])
+        grads = _gcn2_backward(ctx, x, w1, w2, h1, out_rows, grad_rows, ctx.needs_input_grad[:5], ctx.rs,
+                               restricted=True)
         return (*grads, None, None, None, None)
 
 

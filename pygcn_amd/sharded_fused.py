@@ -24,8 +24,8 @@ the pipelined dense halo exchange and the log_softmax in the completing launch).
 import torch
 import torch.distributed as dist
 
-from . import gemm as _gemm, spmm as _spmm
-from .fused import _hidden_layer_stage, _loss_rows_stage, _describe_rows, _list_rows2
+from . import gemm as _gemm
+from .fused import _forward_record, _hidden_layer_stage, _loss_rows_stage, _describe_rows, _list_rows2
 from .sharded import HaloExchange
 from .gemm import _dense_forward
 from .spmm import log_softmax_fusable
@@ -108,25 +108,25 @@ class ShardedGCN2RowsFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, sg, rs, x_local, x_halo, w1, b1, w2, b2, dropout_p, seed):
         ctx.sg, ctx.rs = sg, rs
-        ctx.scale = _spmm.dropout_scale(dropout_p)
+        fw = ctx.fw = _forward_record(dropout_p, b1, b2)      # (what fused._hidden_layer_stage reads)
+        fw.reassoc = True                                      # (fusable() admits no other layer 1)
         f32 = x_local.dtype == torch.float32
         ev = sg._tic(x_local)
         z = sg._spmm(sg.A, x_local, tag="fwd_local", B2=x_halo)
         sg._toc(ev, "fwd")
-        ctx.z_bound = h_bound = None
+        h_bound = None
         if f32:
-            ctx.z_bound = sg.A.inf_norm() * sg.constant_absmax(x_local) * 1.0001
+            fw.z_bound = sg.A.inf_norm() * sg.constant_absmax(x_local) * 1.0001
             h_bound = torch.zeros(1, dtype=torch.float32, device=x_local.device)
         kw = {"dropout_p": dropout_p, "seed": seed, "row_base": sg.r0} if dropout_p > 0.0 else {}
         # (`h1 > 0` as one bit per element for the masked grad_input GEMM: pygcn_amd/fused.py)
-        ctx.keep_bits = None
         if f32 and _gemm.gemm_keep_bits_usable(z, None, dropout_p) and any(ctx.needs_input_grad):
-            ctx.keep_bits = torch.empty((z.shape[0], 8), dtype=torch.int32, device=z.device)
-            kw = dict(kw, keep_bits_out=ctx.keep_bits)
-        h1 = _gemm.layer_gemm(z, w1, ctx.z_bound, h_bound, bias=b1, relu=True, **kw)
+            fw.keep_bits = torch.empty((z.shape[0], 8), dtype=torch.int32, device=z.device)
+            kw = dict(kw, keep_bits_out=fw.keep_bits)
+        h1 = _gemm.layer_gemm(z, w1, fw.z_bound, h_bound, bias=b1, relu=True, **kw)
         if h1 is None:
             raise RuntimeError("sharded one-node path: the layer GEMM declined the operands")
-        ctx.h_bound = h_bound
+        fw.h_bound = h_bound
         if sg.compress_hidden and h1.shape[1] % 32 == 0:
             # h1 is >= 75 % zeros (ReLU + dropout): its halo rows travel as bitmask + values and meet
             # W2 on arrival (ShardedGraph.product_hidden) instead of dense rows of h1·W2 travelling
@@ -135,19 +135,17 @@ class ShardedGCN2RowsFunction(torch.autograd.Function):
             logp = sg.product(_dense_forward(h1, w2, h_bound), bias=b2, log_softmax=True)
         out_rows = logp.index_select(0, rs.rows_user)
         ctx.save_for_backward(z, w1, w2, h1, out_rows)
-        ctx.has_bias = (b1 is not None, b2 is not None)
-        ctx.bias_dtypes = (b1.dtype if b1 is not None else None, b2.dtype if b2 is not None else None)
         return out_rows
 
     @staticmethod
     def backward(ctx, grad_rows):
         z, w1, w2, h1, out_rows = ctx.saved_tensors
-        sg, rs = ctx.sg, ctx.rs
-        need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[4:8]
+        sg, rs, fw = ctx.sg, ctx.rs, ctx.fw
+        need_b2 = ctx.needs_input_grad[7]
         dev, dt = z.device, h1.dtype
         # ---- loss rows (fused._loss_rows_stage), compact [|R_r|, C]
-        gp, colsum = _loss_rows_stage(grad_rows, out_rows, ctx.has_bias[1] and need_b2, rs)
-        grad_b2 = colsum.to(ctx.bias_dtypes[1]) if colsum is not None else None
+        gp, colsum = _loss_rows_stage(grad_rows, out_rows, fw.bias_dtypes[1] is not None and need_b2, rs)
+        grad_b2 = colsum.to(fw.bias_dtypes[1]) if colsum is not None else None
         gp = gp.contiguous()
         # ---- layer 2: the static halo of gradient rows, then the block product (compact in / out)
         ev = sg._tic(gp)
@@ -173,7 +171,5 @@ class ShardedGCN2RowsFunction(torch.autograd.Function):
                 if rs.n2 else grad_sup2.new_zeros(1).float())
         # ---- hidden layer on the rows R2_r (fused._hidden_layer_stage; an empty R2_r is its business)
         _, _, grad_w2, grad_b1, grad_w1 = _hidden_layer_stage(
-            h1, w2, grad_sup2, gs_bound, z, need_w2, need_w1,
-            ctx.bias_dtypes[0] if (ctx.has_bias[0] and need_b1) else None,
-            ctx.scale, ctx.h_bound, ctx.z_bound, ctx.keep_bits, rows=rs, l1_follows_l2=True)
+            fw, h1, w2, grad_sup2, gs_bound, z, ctx.needs_input_grad[4:7], rows=rs, l1_follows_l2=True)
         return None, None, None, None, grad_w1, grad_b1, grad_w2, grad_b2, None, None

@@ -133,7 +133,7 @@ def measure(name, steps, dev):
         res["peak_above_live"] = peaks
     finally:
         fused.set_input_product_cache(False)
-    # ---- the forward kernels of (b), one by one (same calls as fused._gcn2_forward_restricted)
+    # ---- the forward kernels of (b), one by one (same calls as fused._gcn2_forward with the row sets)
     w1, b1, w2, b2 = (t.detach() for t in (model.gc1.weight, model.gc1.bias, model.gc2.weight, model.gc2.bias))
     z = S.spmm_csr(a_rows2, x)
     h1 = G.layer_gemm(z, w1, bias=b1, relu=True)
