@@ -88,7 +88,9 @@ typedef struct gcn_csr_plan {
  * 26: the input side of its evaluator, gcn_eval_workspace_bytes / gcn_eval_ingest / gcn_eval_ingest_backward
  * (GCN_OVER_MLP and PoolLayer, reference pygcn/models.py:333-355, :267-286).  Also additive to 26: gcn_dropout_rows /
  * gcn_csr_take_rows (dropout keyed by a row list and row blocks of a CSR matrix, for the forward pass restricted
- * to the loss rows' receptive field).
+ * to the loss rows' receptive field).  Also additive to 26: gcn_bn_linear_workspace_bytes / gcn_bn_linear_forward /
+ * gcn_bn_linear_backward_sums / gcn_bn_linear_backward_apply (ReLU + BatchNorm folded into the next layer's X·W for
+ * 32-wide layers).
  * 25 (round 4, late): new entry point gcn_gemm_atg256_f32_b3_colsum (the
  * weight gradient with the bias gradient Σ G[rows] as a side result); gcn_gemm_atg256_workspace_bytes grew by
  * 1 KiB per workgroup; struct gcn_gemm_epilogue gained keep_bits_out / mask_bits at its END (zero them);
@@ -904,6 +906,47 @@ int gcn_dropout_rows(int dtype, void *h, int64_t ld, const int64_t *rows, int64_
 int gcn_csr_take_rows(const void *rowptr, int rowptr_is64, const int32_t *col, const float *val, const int64_t *rows,
                       int64_t m, const int32_t *col_map, const void *rowptr_out, int out_is64, int32_t *col_out,
                       float *val_out, int32_t *n_unmapped, void *stream);
+
+/*
+ * BN(relu(z)) · W as one node for 32-wide layers: the fork's apply_bn(F.relu(gc(x, adj))) (reference
+ * pygcn/models.py:49,53) folded into the NEXT layer's X·W (pygcn/layers.py:33), so that the normalised activation
+ * is never written (pygcn_amd/csrc/gcn_normlin.hip).  z, s, ds, dz are contiguous fp32 [n_rows, batch * 32]: batch
+ * samples side by side, the layout of the gcn_bn_*_batched entry points; weight is fp32 [Fin, Fout] row-major
+ * (GraphConvolution's).  With x = relu ? relu(z) : z and xhat = (x - mean) * rstd per column of a window, mean and
+ * rstd fp32 [batch * 32] as gcn_bn_stats_batched returns them:
+ *   gcn_bn_linear_forward         s[:, window j] = xhat[:, window j] · weight.  xhat is formed in fp32 exactly as
+ *                                 gcn_bn_apply_batched forms it (gamma, beta NULL) and the product is an fp32 fmaf
+ *                                 chain (v_mfma_f32_32x32x2_f32).
+ *   gcn_bn_linear_backward_sums   grad_w [Fin, Fout] fp32 = sum over windows and rows of xhat^T · ds, and the DEVICE
+ *                                 double coef [4, batch * 32] in the layout gcn_bn_backward_sums_batched writes
+ *                                 (mean, rstd, sum dy / n, rstd^2 * sum dy (x - mean) / n; dy = ds · weight^T, which
+ *                                 is never stored).  fp32 sums run over one wavefront's slab of rows at most; the 4
+ *                                 wavefronts of a block are added in wave order in double, one partial row per
+ *                                 (window, block); a finish launch adds the partial rows of a window in a fixed
+ *                                 order in double, a second one the windows in window order.  No float atomics,
+ *                                 bitwise reproducible.
+ *   gcn_bn_linear_backward_apply  dz = [z > 0] * rstd * (dy - sum dy / n - xhat * sum (dy xhat) / n), evaluated in
+ *                                 double from coef as gcn_bn_backward_apply_batched does; dz must not alias ds.
+ * A window's s, coef and dz are bitwise those of the batch = 1 call on a contiguous copy of the window.
+ * SHAPE RULE: 2 <= n_rows <= 2^40, Fin = Fout = 32, 1 <= batch <= 65535 (else GCN_E_BADARG, as a NULL pointer);
+ * z, s, ds, dz, weight and the workspace 16-byte aligned, coef 8-byte (GCN_E_ALIGN).
+ * Scratch of gcn_bn_linear_backward_sums (short or NULL: GCN_E_WORKSPACE):
+ *     gcn_bn_linear_workspace_bytes = batch * (B + 1) * 1152 * sizeof(double),
+ *     T = ceil(n_rows / (128 * 512)),  R = 128 * T,  B = ceil(n_rows / R)
+ * — every sweep runs B blocks of 4 wavefronts per window; block b owns the rows [b * R, min((b + 1) * R, n_rows)) and
+ * its wavefront w the rows [b * R + 32 * T * w, b * R + 32 * T * (w + 1)) of them, walked in T tiles of 32 rows (the
+ * last one partial where the slab ends).  0 outside the rule.
+ * (ABI 26, additive.)
+ */
+size_t gcn_bn_linear_workspace_bytes(int64_t n_rows, int64_t Fin, int64_t Fout, int64_t batch);
+int gcn_bn_linear_forward(const float *z, const float *weight, const float *mean, const float *rstd, float *s,
+                          int64_t n_rows, int64_t Fin, int64_t Fout, int64_t batch, int relu, void *stream);
+int gcn_bn_linear_backward_sums(const float *ds, const float *z, const float *weight, const float *mean,
+                                const float *rstd, int64_t n_rows, int64_t Fin, int64_t Fout, int64_t batch,
+                                int relu, float eps, float *grad_w, double *coef, void *workspace,
+                                size_t workspace_bytes, void *stream);
+int gcn_bn_linear_backward_apply(const float *ds, const float *z, const float *weight, const double *coef, float *dz,
+                                 int64_t n_rows, int64_t Fin, int64_t Fout, int64_t batch, int relu, void *stream);
 
 #ifdef __cplusplus
 }

@@ -142,6 +142,10 @@ SIGNATURES = {
                               p, p, p, p, p, p, p, p, sz, p]),
     "gcn_dropout_rows": (i, [i, p, i64, p, i64, i64, f32, ctypes.c_uint64, p, i64, p]),
     "gcn_csr_take_rows": (i, [p, i, p, p, p, i64, p, p, i, p, p, p, p]),
+    "gcn_bn_linear_workspace_bytes": (sz, [i64, i64, i64, i64]),
+    "gcn_bn_linear_forward": (i, [p, p, p, p, p, i64, i64, i64, i64, i, p]),
+    "gcn_bn_linear_backward_sums": (i, [p, p, p, p, p, i64, i64, i64, i64, i, f32, p, p, p, sz, p]),
+    "gcn_bn_linear_backward_apply": (i, [p, p, p, p, p, i64, i64, i64, i64, i, p]),
 }
 EXPORTS = tuple(SIGNATURES)
 

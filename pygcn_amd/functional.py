@@ -30,6 +30,9 @@ from pygcn_amd.evaluator import evaluator_ingest  # noqa: E402,F401
 # layers with ReLU (+ BatchNorm) on cat(h, x[:, d:]) — as fused sweeps that recompute instead of storing:
 # pygcn_amd/head.py
 from pygcn_amd.head import vertex_mlp  # noqa: E402,F401
+# apply_bn(F.relu(.)) folded into the next layer's torch.mm(input, weight) (pygcn/models.py:49-56, layers.py:33) for
+# its 32-wide layers, the normalised activation never written: pygcn_amd/normlin.py
+from pygcn_amd.normlin import relu_batch_norm_linear  # noqa: E402,F401
 
 
 class NLLGrad(torch.Tensor):

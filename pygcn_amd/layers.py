@@ -139,6 +139,15 @@ class GraphConvolution(Module):
         _require_cuda(wide, "input")
         return SpMMFunction.apply(as_graph(adj), wide, bias, relu)
 
+    def aggregate(self, support, adj, k=1, relu=False):
+        """The layer's second half on a support the caller formed: adj · support + bias (ReLU), support
+        [N, k·Fout] being k samples side by side — for a caller that computes X·W as part of another node
+        (functional.relu_batch_norm_linear)."""
+        if support.dim() != 2 or support.shape[1] != k * self.out_features:
+            raise RuntimeError(f"GraphConvolution.aggregate: support must be [N, {k}*{self.out_features}], "
+                               f"got {tuple(support.shape)}")
+        return self._aggregate_wide(support, adj, k, relu)
+
     def forward_wide(self, wide, adj, k, relu=False):
         """The layer on k samples that STAY side by side: wide [N, k·Fin] -> [N, k·Fout], both
         contiguous with sample j in the columns [j·F, (j+1)·F) — the layout _forward_batched aggregates

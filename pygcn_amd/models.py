@@ -19,6 +19,7 @@ from pygcn_amd.attention import vertex_attention, vertex_mean  # noqa: E402
 from pygcn_amd.evaluator import evaluator_ingest  # noqa: E402
 from pygcn_amd.head import vertex_mlp  # noqa: E402
 from pygcn_amd.norm import relu_batch_norm  # noqa: E402
+from pygcn_amd.normlin import relu_batch_norm_linear  # noqa: E402
 from pygcn_amd.pool import masked_mean_pool  # noqa: E402
 from pygcn_amd.select import sample_without_replacement, selection_log_prob, topk_flag  # noqa: E402
 from pygcn_amd.sharded import ShardedGraph  # noqa: E402
@@ -168,15 +169,22 @@ class GCNBatchNorm(nn.Module):
 
     A 3-D input [k, N, nfeat] is k samples over the same graph (the fork's evaluator GCN_OVER_MLP
     loops over them, :343-349): the result is [k, N, nclass], each sample normalised on its own, all
-    k in one pass (_forward_batched)."""
+    k in one pass (_forward_batched).
 
-    def __init__(self, nfeat, nhid, nclass, dropout, NN=None):
+    `fused_norm=True` (opt-in): layers 2 and 3 take ReLU + BatchNorm and their own X·W as ONE node,
+    `functional.relu_batch_norm_linear` — the normalised activation is neither written nor kept for the
+    backward pass — and aggregate its result (GraphConvolution.aggregate); layer 1 is unchanged.  The HIP
+    sweeps carry 32 -> 32 layers (the fork's widths); other widths run the same composition of nodes as the
+    default.  Parameters and state_dict keys do not change."""
+
+    def __init__(self, nfeat, nhid, nclass, dropout, NN=None, fused_norm=False):
         super(GCNBatchNorm, self).__init__()
         self.gc1 = GraphConvolution(nfeat, nhid)
         self.gc2 = GraphConvolution(nhid, nhid)
         self.gc3 = GraphConvolution(nhid, nclass)
         self.dropout = dropout
         self.NN = NN
+        self.fused_norm = bool(fused_norm)
 
     def forward(self, x, adj):
         if isinstance(adj, ShardedGraph):
@@ -184,6 +192,8 @@ class GCNBatchNorm(nn.Module):
                                "statistics run over all vertices, and cross-rank statistics are not built")
         if x.dim() == 3:
             return self._forward_batched(x, adj)
+        if self.fused_norm:
+            return self._fused_tail(self.gc1(x, adj), adj, 1)
         x = relu_batch_norm(self.gc1(x, adj))
         x = relu_batch_norm(self.gc2(x, adj))
         return self.gc3(x, adj, relu=True)
@@ -208,9 +218,16 @@ class GCNBatchNorm(nn.Module):
         if isinstance(adj, ShardedGraph):
             raise RuntimeError("GCNBatchNorm: a ShardedGraph adjacency is not supported — BatchNorm's "
                                "statistics run over all vertices, and cross-rank statistics are not built")
+        if self.fused_norm:
+            return self._fused_tail(self.gc1.forward_wide(wide, adj, k), adj, k)
         h = relu_batch_norm(self.gc1.forward_wide(wide, adj, k), batch=k)
         h = relu_batch_norm(self.gc2.forward_wide(h, adj, k), batch=k)
         return self.gc3.forward_wide(h, adj, k, relu=True)
+
+    def _fused_tail(self, z, adj, k):
+        """Layers 2 and 3 on layer 1's output z [N, k·nhid], BatchNorm(relu(.)) · W as one node each."""
+        z = self.gc2.aggregate(relu_batch_norm_linear(z, self.gc2.weight, batch=k), adj, k)
+        return self.gc3.aggregate(relu_batch_norm_linear(z, self.gc3.weight, batch=k), adj, k, relu=True)
 
 
 class SoftGeneratorPoolMLP(nn.Module):
@@ -433,12 +450,14 @@ class GCN_OVER_MLP(nn.Module):
     the vertex flag arrives on its own instead of as the last column of x, which is then ignored — the
     device-friendly form of `cat(..., vac_flag)` in the fork's generator training (reference
     pygcn/policy-generator.py:398-420), where the flag is the only thing that receives gradient: x stays a
-    constant, and layer 1 of the GCN forms no input gradient."""
+    constant, and layer 1 of the GCN forms no input gradient.
+
+    `fused_norm=True` (opt-in) is passed on to GCNBatchNorm."""
 
     def __init__(self, nfeat, nhid, nclass, dropout, NN, linear_nin, linear_nhid1, linear_nhid2, dim_touched=None,
-                 linear_nout=1, linear_bias=True):
+                 linear_nout=1, linear_bias=True, fused_norm=False):
         super(GCN_OVER_MLP, self).__init__()
-        self.GCNLayer = GCNBatchNorm(nfeat, nhid, nclass, dropout, NN)
+        self.GCNLayer = GCNBatchNorm(nfeat, nhid, nclass, dropout, NN, fused_norm=fused_norm)
         self.PoolLayer = PoolLayer()
         self.MLPLayers = MLPLayers(linear_nin, linear_nhid1, linear_nhid2, linear_nout, bias=linear_bias)
         self.dim_touched = dim_touched
@@ -462,7 +481,8 @@ class GCN_OVER_MLP(nn.Module):
 def get_model(config, model_name='GCN'):
     """The fork's `get_model` (reference pygcn/models.py:440-460): `config` is any object with its attribute
     names — gcn_nfeat, gcn_nhid, gcn_nclass, gcn_dropout, NN, dim_touched, linear_nin, linear_nhid1,
-    linear_nhid2, linear_nout, linear_bias, and optionally fused_head (the two generators' opt-in).  'MLP',
+    linear_nhid2, linear_nout, linear_bias, and optionally fused_head (the two generators' opt-in) and fused_norm
+    (the evaluator's).  'MLP',
     'GNN_OVER_MLP', 'Generator', 'Hierarchical_Generator' and 'SoftGenerator' give the classes of this module.
     'GCN', the default, is broken in the fork (it passes six
     arguments to a five-argument GCN, :444: a TypeError) and raises TypeError here too; the fork lets an unknown
@@ -481,7 +501,7 @@ def get_model(config, model_name='GCN'):
                                                     bias=c.linear_bias))
     if model_name == 'GNN_OVER_MLP':
         return GCN_OVER_MLP(*gcn, c.linear_nin, c.linear_nhid1, c.linear_nhid2, c.dim_touched, c.linear_nout,
-                            c.linear_bias)
+                            c.linear_bias, getattr(c, 'fused_norm', False))
     if model_name == 'Generator':
         return Generator(*gcn, c.linear_nin, c.linear_nhid1, c.linear_nhid2, c.dim_touched, c.linear_nout,
                          c.linear_bias, getattr(c, 'fused_head', False))
