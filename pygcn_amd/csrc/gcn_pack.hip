@@ -219,32 +219,61 @@ __device__ __forceinline__ uint32_t or16(uint32_t v)       // OR over each row o
     return v;
 }
 
+// The slot is put together in a wave-private 512-byte LDS image (header words from lanes 0..2 of the quarter, a
+// value at its rank) and leaves as ONE 8-byte store per lane: 512 contiguous bytes, four whole 128-byte lines per
+// wave instruction.  A wave carries kPack512RowsPerWave consecutive rows, their 16-byte loads issued first.  Words
+// past a quarter's count carry whatever the image held (the format leaves them undefined; no reader uses them).
+// Only the wave's own lanes touch its images, so a wavefront-scope fence orders write and read: no workgroup
+// barrier (the last block's waves may have no rows and return).
+#ifndef GCN_PACK512_ROWS_PER_WAVE
+#define GCN_PACK512_ROWS_PER_WAVE 2
+#endif
+constexpr int kPack512RowsPerWave = GCN_PACK512_ROWS_PER_WAVE;
+constexpr int kPack512RowsPerBlock = kRowsPerBlock * kPack512RowsPerWave;     // (kRowsPerBlock waves)
+
 __global__ __launch_bounds__(kWave *kRowsPerBlock) void pack512_kernel(const float *__restrict__ src, int64_t ld,
                                                                        int64_t m, uint32_t *__restrict__ slots)
 {
+    constexpr int R = kPack512RowsPerWave;
+    __shared__ __attribute__((aligned(16))) uint32_t image_all[kRowsPerBlock * R * 128];
     const int lane = threadIdx.x & (kWave - 1);
-    const int64_t r = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
-    if (r >= m) return;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t r0 = ((int64_t)blockIdx.x * kRowsPerBlock + wave) * R;
+    if (r0 >= m) return;
+    const int nr = (int)(m - r0 < R ? m - r0 : R);           // wave-uniform
     const int q = lane >> 4, i = lane & 15;
-    const uint4 v = *(const uint4 *)(src + r * ld + 16 * i + 4 * q);
-    const uint32_t x[4] = {v.x, v.y, v.z, v.w};
-    uint32_t nib = 0u;
+    uint32_t *image = image_all + wave * (R * 128);
+    uint4 v[R];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) nib |= (x[j] != 0u ? 1u : 0u) << j;
-    const uint32_t lo = or16(i < 8 ? nib << (4 * i) : 0u), hi = or16(i >= 8 ? nib << (4 * (i - 8)) : 0u);
-    const unsigned long long mask = ((unsigned long long)hi << 32) | lo;
-    int rank = __builtin_popcountll(mask & ((1ull << (4 * i)) - 1ull));
-    uint32_t *sub = slots + r * 128 + 32 * q;
-    if (i == 0) {
-        sub[0] = lo;
-        sub[1] = hi;
-        sub[2] = (uint32_t)__builtin_popcountll(mask);
+    for (int k = 0; k < R; ++k)    // (rows past m: the last row again, loaded and not stored)
+        v[k] = *(const uint4 *)(src + (r0 + (k < nr ? k : nr - 1)) * ld + 16 * i + 4 * q);
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        const uint32_t x[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+        uint32_t nib = 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) nib |= (x[j] != 0u ? 1u : 0u) << j;
+        const uint32_t lo = or16(i < 8 ? nib << (4 * i) : 0u), hi = or16(i >= 8 ? nib << (4 * (i - 8)) : 0u);
+        const unsigned long long mask = ((unsigned long long)hi << 32) | lo;
+        int rank = __builtin_popcountll(mask & ((1ull << (4 * i)) - 1ull));
+        uint32_t *sub = image + k * 128 + 32 * q;
+        if (i < 3) sub[i] = i == 0 ? lo : i == 1 ? hi : (uint32_t)__builtin_popcountll(mask);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if ((nib >> j) & 1u) {
+                if (rank < kPack512Cap) sub[3 + rank] = x[j];
+                ++rank;
+            }
+        }
     }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if ((nib >> j) & 1u) {
-            if (rank < kPack512Cap) sub[3 + rank] = x[j];
-            ++rank;
+    for (int k = 0; k < R; ++k) {
+        if (k < nr) {
+            const uint2 w = *(const uint2 *)(image + k * 128 + 2 * lane);
+            *(uint2 *)(slots + (r0 + k) * 128 + 2 * lane) = w;
         }
     }
 }
@@ -325,8 +354,9 @@ int gcn_rows_pack512(const float *src, int64_t ld, int64_t m, uint32_t *slots, v
     if (src == nullptr || slots == nullptr) return gcn_internal_fail(GCN_E_BADARG, "gcn_rows_pack512: NULL pointer");
     if ((((uintptr_t)src) | ((uintptr_t)slots)) % 16 != 0)
         return gcn_internal_fail(GCN_E_ALIGN, "gcn_rows_pack512: 16-byte alignment required");
-    if ((m + kRowsPerBlock - 1) / kRowsPerBlock > INT32_MAX) return gcn_internal_fail(GCN_E_BADARG, "gcn_rows_pack512: too many rows");
-    const dim3 grid((unsigned)((m + kRowsPerBlock - 1) / kRowsPerBlock)), block(kWave * kRowsPerBlock);
+    const int64_t blocks = (m + kPack512RowsPerBlock - 1) / kPack512RowsPerBlock;
+    if (blocks > INT32_MAX) return gcn_internal_fail(GCN_E_BADARG, "gcn_rows_pack512: too many rows");
+    const dim3 grid((unsigned)blocks), block(kWave * kRowsPerBlock);
     hipLaunchKernelGGL(pack512_kernel, grid, block, 0, (hipStream_t)stream, src, ld, m, slots);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, "gcn_rows_pack512 launch");

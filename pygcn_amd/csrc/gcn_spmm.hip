@@ -592,9 +592,18 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void spmm_wide_kernel(KParam
 //   * per stored entry ONE 8-byte buffer load per lane at the lane-static offset 8 * lane: lane (q, i) =
 //     (lane >> 4, lane & 15) holds words 2i, 2i + 1 of sub-slot q; the ladder is that of wide_stream (D loads in
 //     flight, no branch, a slot past the tile has num_records 0 and reads zeros = an empty mask);
-//   * lane (q, i) OWNS columns 16 i + 4 q .. + 3 = bits 4i .. 4i + 3 of its quarter: the mask and the count come
-//     from lanes 0 / 1 of its row of 16 (DPP row broadcast), its values start at word 3 + popcount(mask below
-//     bit 4i) and span at most three lanes of the row: five ds_bpermute, then selects by the nibble;
+//   * lane (q, i) OWNS columns 16 i + 4 q .. + 3 = bits 4i .. 4i + 3 of its quarter.  The loaded 8 bytes per lane
+//     are STAGED in a wave-private LDS copy of the slot (one ds_write_b64 per lane; D copies per wave, one per
+//     load in flight): the mask is then a broadcast read of words 0, 1 of the sub-slot, and the lane's up to four
+//     values are the consecutive words w0 .. w0 + 3, w0 = 3 + popcount(mask below bit 4i) — one computed address
+//     and fixed offsets — handed out by the nibble (v_bfe_i32 bit masks, v_and / v_bfi: nothing goes through VCC).
+//     The D copies are written; then the masks are read four entries at a time and the values two entries at a
+//     time (what 72 registers leave room for): LDS latency is paid per group, never per entry.
+//     Only the wave's own lanes touch its copies, so wavefront-scope fences order them: there is NO workgroup
+//     barrier in this kernel (waves of a block run different trip counts and return early);
+//   * LDS image of a copy (kStageWords): sub-slot q starts at word 42 q + 6 (q & 1) = 0, 48, 84, 132 — 36 words
+//     each, because a lane of a full quarter reads up to word 35 (selected away), and the two quarters that share
+//     a 32-lane half of a ds_read_b32 sit 16 banks apart (their value words run over the same range of ranks);
 //   * the same fmaf per (entry, column) in the same order as the dense launch — a cleared bit contributes
 //     fmaf(a, 0, acc) as the dense zero does — so the result is bit-identical;
 //   * an entry whose slot reports an overflowed quarter (count > 29; wave-uniform test on the loaded words)
@@ -613,65 +622,85 @@ __device__ __forceinline__ u32x2 slot_load8(uint64_t base, uint32_t nbytes, uint
     return __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, 0, 0);
 }
 
-template <int N> __device__ __forceinline__ uint32_t row_bcast(uint32_t v)    // lane N of every row of 16 lanes
-{
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x150 + N, 0xF, 0xF, true);   // (every lane has a source)
-}
-
 constexpr int kPackSlotBytes = 512;
 constexpr uint32_t kPackCap = GCN_PACK512_CAPACITY;
+// LDS image of one staged slot, in words: sub-slots at 0, 48, 84, 132, 36 words each (see above)
+constexpr int kStageWords = 168;
+// An OVERFLOWED quarter (its values come from the dense row) may have all 64 bits set: its lanes' discarded
+// reads reach word 3 + 60 + 3 of the sub-slot, 31 words past the copy — into the wave's next copy, the next
+// wave's, or this tail behind the last wave's.
+constexpr int kStageTailWords = 32;
+template <int D> constexpr int stage_block_words() { return kWavesPerBlock * D * kStageWords + kStageTailWords; }
+
+// Orders this wave's LDS writes and reads of its own copies (no other wave touches them): compiler fences of
+// wavefront scope, no instruction and no workgroup barrier.
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 template <int D, bool ROWS>
-__device__ __forceinline__ void packed_stream(const KParams &p, const int32_t *__restrict__ colp,
+__device__ __forceinline__ void packed_stream(const KParams &p, uint32_t *stage, const int32_t *__restrict__ colp,
                                               const float *__restrict__ valp, int ne, int lane, float (&acc)[4],
                                               int rel_end, int nr, int64_t row0, int f, const float (&bias)[4])
 {
-    const int i = lane & 15;
+    const int q = lane >> 4, i = lane & 15;
     const uint32_t ldb_bytes = (uint32_t)(p.ldb * 4);                    // the dense rows (overflowed slots)
     const uint32_t voff = (uint32_t)lane * 8u;
-    const unsigned long long below = (1ull << (4 * i)) - 1ull;
-    const int row_lane0 = (lane & 48) << 2;              // 4 * the first lane of this lane's row of 16
+    // lane-static: this lane's sub-slot in a staged copy and its own two words there; which mask word holds its
+    // nibble and where; the bits below its nibble in either mask word
+    uint32_t *const sub = stage + 42 * q + 6 * (q & 1);
+    uint32_t *const mine = sub + 2 * i;
+    const bool upper = i >= 8;
+    const uint32_t sh = 4u * (uint32_t)(i & 7);
+    const uint32_t below_lo = upper ? ~0u : (1u << sh) - 1u, below_hi = upper ? (1u << sh) - 1u : 0u;
+    const bool cnt_lane = i == 1;                         // loads words 2, 3 of its sub-slot: .x is the count
     int r = 0;
     int rend = ROWS ? readlane_i(rel_end, 0) : INT_MAX;
-    auto consume = [&](int e, const u32x2 &raw, float a, int c) {
+    // store row rr of the item and start the next one
+    auto emit = [&](int rr) {
+        store_out<float, 4, kWave, 0>(p, row0 + rr, f, true, acc, bias);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = 0.f;
+    };
+    // the lane's four columns of a staged slot: `nibs` = its mask word from its nibble on, v = the words
+    // w0 .. w0 + 3 of its sub-slot.  Bit by bit of the nibble, "take the head of the queue if the bit is set" — a
+    // cleared bit leaves +0.0.  b[k] is all ones or zero (v_bfe_i32 of one bit), a select is v_bfi, a take v_and:
+    // 15 instructions, none through VCC.  (v_bfi by name: written as and / or, the selects come back as compares,
+    // v_cndmask and twice the instructions.)
+    auto expand = [](uint32_t nibs, const uint32_t (&v)[4], float (&x)[4]) {
+        uint32_t b[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) b[k] = (uint32_t)__builtin_amdgcn_sbfe((int)nibs, (uint32_t)k, 1u);
+        auto sel = [](uint32_t m, uint32_t yes, uint32_t no) {
+            uint32_t d;
+            asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(d) : "v"(m), "v"(yes), "v"(no));
+            return d;
+        };
+        uint32_t q0 = v[0], q1 = v[1], q2 = v[2];
+        x[0] = __uint_as_float(q0 & b[0]);
+        q0 = sel(b[0], q1, q0); q1 = sel(b[0], q2, q1); q2 = sel(b[0], v[3], q2);
+        x[1] = __uint_as_float(q0 & b[1]);
+        q0 = sel(b[1], q1, q0); q1 = sel(b[1], q2, q1);
+        x[2] = __uint_as_float(q0 & b[2]);
+        q0 = sel(b[2], q1, q0);
+        x[3] = __uint_as_float(q0 & b[3]);
+    };
+    // entry e with value a and the lane's four columns x of the gathered row; `over`: the slot overflowed
+    // (wave-uniform), column c's dense row stands in
+    auto consume = [&](int e, float (&x)[4], bool over, float a, int c) {
         if (ROWS) {
             while (e >= rend) {   // row finished (loop: rows without stored entries follow)
-                store_out<float, 4, kWave, 0>(p, row0 + r, f, true, acc, bias);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) acc[k] = 0.f;
+                emit(r);
                 ++r;
                 rend = readlane_i(rel_end, r);
             }
         }
-        const uint32_t mlo = row_bcast<0>(raw.x), mhi = row_bcast<0>(raw.y), cnt = row_bcast<1>(raw.x);
-        float x[4];
-        if (__ballot(cnt > kPackCap) != 0ull) {      // wave-uniform and rare: a quarter did not fit its sub-slot
+        if (over) {                                  // wave-uniform and rare: a quarter did not fit its sub-slot
             const u32x4 d = row_load16((uint64_t)p.B + (uint64_t)(uint32_t)c * ldb_bytes, 1024u, (uint32_t)f * 4u);
             Elem<float, 4>::unpack(__builtin_bit_cast(f32x4, d), x);
-        } else {
-            const unsigned long long m = ((unsigned long long)mhi << 32) | mlo;
-            const uint32_t nib = (uint32_t)(m >> (4 * i)) & 0xFu;
-            const int w0 = 3 + __builtin_popcountll(m & below);          // word of this lane's first value
-            // ... in lane w0 >> 1 of the row of 16, and the next two (byte addresses of ds_bpermute: 4 * lane)
-            const int w2 = w0 << 1;
-            const int a0 = row_lane0 | (w2 & 60), a1 = row_lane0 | ((w2 + 4) & 60), a2 = row_lane0 | ((w2 + 8) & 60);
-            const int s0 = __builtin_amdgcn_ds_bpermute(a0, (int)raw.x), s1 = __builtin_amdgcn_ds_bpermute(a0, (int)raw.y);
-            const int s2 = __builtin_amdgcn_ds_bpermute(a1, (int)raw.x), s3 = __builtin_amdgcn_ds_bpermute(a1, (int)raw.y);
-            const int s4 = __builtin_amdgcn_ds_bpermute(a2, (int)raw.x);
-            // single-level selects (one v_cndmask each): first the four words from w0 on (an odd w0 starts in
-            // the upper word of its lane), then, bit by bit of the nibble, "take the head of the queue if the
-            // bit is set" — a cleared bit leaves +0.0
-            const bool odd = (w0 & 1) != 0;
-            float q0 = __int_as_float(odd ? s1 : s0), q1 = __int_as_float(odd ? s2 : s1),
-                  q2 = __int_as_float(odd ? s3 : s2), q3 = __int_as_float(odd ? s4 : s3);
-            const bool b0 = (nib & 1u) != 0u, b1 = (nib & 2u) != 0u, b2 = (nib & 4u) != 0u, b3 = (nib & 8u) != 0u;
-            x[0] = b0 ? q0 : 0.f;
-            q0 = b0 ? q1 : q0; q1 = b0 ? q2 : q1; q2 = b0 ? q3 : q2;
-            x[1] = b1 ? q0 : 0.f;
-            q0 = b1 ? q1 : q0; q1 = b1 ? q2 : q1;
-            x[2] = b2 ? q0 : 0.f;
-            q0 = b2 ? q1 : q0;
-            x[3] = b3 ? q0 : 0.f;
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) acc[k] = fmaf(a, x[k], acc[k]);
@@ -695,23 +724,70 @@ __device__ __forceinline__ void packed_stream(const KParams &p, const int32_t *_
                 x[j] = slot_load8((uint64_t)p.packed + (uint64_t)(uint32_t)cc[j] * (uint64_t)kPackSlotBytes,
                                   ok ? (uint32_t)kPackSlotBytes : 0u, voff);
             }
+            // stage the D slots (the previous group's reads come first); one test per group tells whether any of
+            // them overflowed (the largest count word: .x of lane 1 of a quarter)
+            wave_sync();
+            uint32_t top = 0u;
 #pragma unroll
-            for (int j = 0; j < D; ++j)
-                consume(min(t + k + j, ne - 1), x[j], readlane_f(vv, k + j), cc[j]);
+            for (int j = 0; j < D; ++j) {
+                *(u32x2 *)(mine + j * kStageWords) = x[j];
+                top = max(top, x[j].x);
+            }
+            const bool any_over = __ballot(cnt_lane && top > kPackCap) != 0ull;
+            wave_sync();
+            // kMaskGroup masks at a time -> per entry the lane's nibble and the place of its first value; then,
+            // kValueGroup entries at a time, the value words and the arithmetic.  (The group sizes are what 72
+            // registers = 7 waves per SIMD leave room for: LDS latency is paid per group, not per entry.)
+            constexpr int kMaskGroup = 4, kValueGroup = 2;
+            static_assert(D % kMaskGroup == 0 && kMaskGroup % kValueGroup == 0, "groups");
+#pragma unroll
+            for (int g0 = 0; g0 < D; g0 += kMaskGroup) {
+                uint32_t nibs[kMaskGroup];
+                const uint32_t *first[kMaskGroup];
+                u32x2 h[kMaskGroup];
+                wave_sync();        // (keeps these reads behind the previous group's arithmetic)
+#pragma unroll
+                for (int j = 0; j < kMaskGroup; ++j) h[j] = *(const u32x2 *)(sub + (g0 + j) * kStageWords);
+#pragma unroll
+                for (int j = 0; j < kMaskGroup; ++j) {
+                    nibs[j] = (upper ? h[j].y : h[j].x) >> sh;
+                    int w0 = __builtin_popcount(h[j].x & below_lo) + __builtin_popcount(h[j].y & below_hi);
+                    asm("" : "+v"(w0));      // (keeps the sum in v_bcnt's addend: the scaling by 4 comes after)
+                    first[j] = sub + (g0 + j) * kStageWords + 3 + w0;        // (over: see kStageTailWords)
+                }
+#pragma unroll
+                for (int g = 0; g < kMaskGroup; g += kValueGroup) {
+                    uint32_t v[kValueGroup][4];
+                    float xs[kValueGroup][4];
+                    wave_sync();    // (keeps these reads behind the previous group's arithmetic)
+#pragma unroll
+                    for (int j = 0; j < kValueGroup; ++j)
+#pragma unroll
+                        for (int w = 0; w < 4; ++w) v[j][w] = first[g + j][w];
+#pragma unroll
+                    for (int j = 0; j < kValueGroup; ++j) expand(nibs[g + j], v[j], xs[j]);
+#pragma unroll
+                    for (int j = 0; j < kValueGroup; ++j) {
+                        const int e = g0 + g + j;                            // the entry's place among the D
+                        consume(min(t + k + e, ne - 1), xs[j],
+                                any_over && __ballot(sub[e * kStageWords + 2] > kPackCap) != 0ull,
+                                readlane_f(vv, k + e), cc[e]);
+                    }
+                }
+            }
         }
     }
     if (ROWS) {
         while (r < nr) {   // last row of the item and any trailing empty rows
-            store_out<float, 4, kWave, 0>(p, row0 + r, f, true, acc, bias);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc[k] = 0.f;
+            emit(r);
             ++r;
         }
     }
 }
 
 template <typename IdxT, int D>
-__global__ __launch_bounds__(kWave *kWavesPerBlock) void spmm_wide_packed_kernel(KParams p)
+__global__ __launch_bounds__(kWave *kWavesPerBlock) __attribute__((amdgpu_waves_per_eu(7, 8)))
+void spmm_wide_packed_kernel(KParams p)
 {
     const int lane = threadIdx.x & (kWave - 1);
     const int item =
@@ -720,13 +796,16 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void spmm_wide_packed_kernel
     const int f = 16 * (lane & 15) + 4 * (lane >> 4);          // (F = 256: every lane holds four columns)
     const IdxT *__restrict__ rp = (const IdxT *)p.rowptr;
     float acc[4] = {0.f, 0.f, 0.f, 0.f}, bias[4] = {0.f, 0.f, 0.f, 0.f};
+    // D staged slot copies per wave, private to it (packed_stream; no __syncthreads anywhere below)
+    __shared__ __attribute__((aligned(16))) uint32_t stage_all[stage_block_words<D>()];
+    uint32_t *stage = stage_all + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * (D * kStageWords);
 
     if (item < p.n_chunks) {
         // ---- one chunk of a long row -> fp32 partial slab
         const int row = p.chunk_row[item];
         const int64_t e0 = p.chunk_e0[item];
         const int64_t e1 = min(e0 + (int64_t)p.long_thresh, (int64_t)rp[row + 1]);
-        packed_stream<D, false>(p, p.col + e0, p.val + e0, (int)(e1 - e0), lane, acc, 0, 0, 0, f, bias);
+        packed_stream<D, false>(p, stage, p.col + e0, p.val + e0, (int)(e1 - e0), lane, acc, 0, 0, 0, f, bias);
         float *dst = p.partial + (int64_t)item * p.F + f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) dst[k] = acc[k];
@@ -743,7 +822,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void spmm_wide_packed_kernel
 #pragma unroll
         for (int k = 0; k < 4; ++k) bias[k] = p.bias[f + k];
     }
-    packed_stream<D, true>(p, p.col + ea, p.val + ea, ne, lane, acc, rel_end, nr, (int64_t)ra, f, bias);
+    packed_stream<D, true>(p, stage, p.col + ea, p.val + ea, ne, lane, acc, rel_end, nr, (int64_t)ra, f, bias);
 }
 
 // ------------------------------------------------------------------------------------------
