@@ -16,11 +16,17 @@ OUT = os.path.join(HERE, "csrc", "libgcn_spmm.so")
 ARCH = "gfx950"
 
 
+def deps():
+    """What the library is built from: the sources, the public header and every internal header beside the sources."""
+    csrc = os.path.join(HERE, "csrc")
+    internal = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h"))
+    return SRCS + [os.path.join(ROOT, "include", "gcn_spmm.h")] + internal
+
+
 def needs_build():
     if not os.path.exists(OUT):
         return True
-    deps = SRCS + [os.path.join(ROOT, "include", "gcn_spmm.h")]
-    return any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps)
+    return any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps())
 
 
 def build(force=False, verbose=True):

@@ -52,9 +52,7 @@
 #include <cstdio>
 
 #include "gcn_spmm.h"
-
-int gcn_internal_fail(int code, const char *msg);
-int gcn_internal_fail_hip(int hip_error, const char *where);
+#include "gcn_internal.h"
 
 namespace {
 
@@ -63,10 +61,6 @@ constexpr int kTileFloats = 8192;        // the LDS image, 32 KiB
 constexpr int64_t kBlocks = 2048;        // slabs of rows = partial rows
 constexpr int64_t kMaxBatch = 65535;     // sample groups ride on gridDim.y
 constexpr int64_t kMaxF = 64;
-
-// a / D for 0 <= a < 2^13 and 1 <= D <= 2^13 given r = 1.0f / D: (a + 0.5) / D is at least 1 / (2 D) away from
-// an integer and the fp32 evaluation is within 2^-22 * a / D of it — the truncation is exact
-__device__ __forceinline__ int fdiv(int a, float r) { return (int)(((float)a + 0.5f) * r); }
 
 struct Shape {
     int P, SP, BS, groups, rows_per_block;
@@ -305,19 +299,6 @@ bool shape_ok(int64_t n_rows, int64_t F, int64_t d, int64_t batch)
 {
     return n_rows >= 1 && n_rows <= (int64_t)INT32_MAX * kBlocks && F >= 2 && F <= kMaxF && d >= 0 && d <= F - 1 &&
            batch >= 1 && batch <= kMaxBatch;
-}
-
-int bad(const char *who, int code, const char *what)
-{
-    char msg[200];
-    std::snprintf(msg, sizeof msg, "%s: %s", who, what);
-    return gcn_internal_fail(code, msg);
-}
-
-int launched(const char *who)
-{
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, who);
 }
 
 bool off(const void *ptr, uintptr_t a) { return (uintptr_t)ptr % a != 0; }

@@ -56,23 +56,7 @@
 #include <cstdio>
 
 #include "gcn_spmm.h"
-
-int gcn_internal_fail(int code, const char *msg);
-int gcn_internal_fail_hip(int hip_error, const char *where);
-
-// keep-threshold of the fused dropout: an element is kept iff its 16-bit field >= round(p * 2^16),
-// clamped to [1, 65535] for p > 0 (0 = dropout off) — include/gcn_spmm.h, struct gcn_epilogue
-static inline uint32_t gcn_dropout_threshold16(float p)
-{
-    if (!(p > 0.f)) return 0u;
-    const double t = (double)p * 65536.0 + 0.5;
-    return (uint32_t)std::min(65535.0, std::max(1.0, (double)(int64_t)t));
-}
-// (the scale of the QUANTISED keep probability, as in gcn_spmm.hip: E[dropout(x)] = x exactly)
-static inline float gcn_dropout_scale16(uint32_t thresh)
-{
-    return thresh == 0u ? 1.f : 65536.f / (float)(65536u - thresh);
-}
+#include "gcn_internal.h"
 
 namespace {
 
@@ -88,12 +72,7 @@ constexpr int kStage = 2;                          // K steps of W staged per ba
 constexpr int kStageBytes = kStage * kChunkBytes;
 constexpr int kWLoads = kStageBytes / 16 / kThreads;   // 16-byte pieces of a W stage per thread
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float bf16_round(float x)   // value of x rounded to bf16, as a float
 {
@@ -438,29 +417,10 @@ struct H2Epi {
     const uint32_t *mask_bits;
 };
 
-// Philox4x32-10 — the SAME keep function of (seed, row, f) as the SpMM epilogue (gcn_spmm.hip,
-// include/gcn_spmm.h): block = ((f >> 4) << 1) | ((f >> 2) & 1), eight 16-bit fields per call.  A
-// lane of the transposed accumulator tile stores columns 32nb + 8g + 4h + (0..3) (h = lane half),
-// so groups g = 2q and 2q + 1 are fields 0..3 and 4..7 of ONE block: one call per 8 elements.
-__device__ __forceinline__ void h2_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                          uint32_t k0, uint32_t k1, uint32_t (&out)[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        // (one 32 x 32 -> 64 multiply per product — v_mad_u64_u32 — instead of a mul_hi + mul_lo
-        //  pair: integer multiplies run at a quarter of the VALU rate and dominate the epilogue)
-        const uint64_t p0 = (uint64_t)0xD2511F53u * (uint64_t)c0, p1 = (uint64_t)0xCD9E8D57u * (uint64_t)c2;
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+// The dropout's keep function of (seed, row, f) and its generator: gcn_internal.h, above philox4x32_10 (the
+// GEMMs use the wide product form).  A lane of the transposed accumulator tile stores columns
+// 32nb + 8g + 4h + (0..3) (h = lane half), so groups g = 2q and 2q + 1 are fields 0..3 and 4..7 of ONE block:
+// one call per 8 elements.
 
 // 16 bytes per lane straight from global memory into LDS (asynchronous, counted by vmcnt like a
 // load): the wave's 64 x 16 bytes land contiguously at LDS byte address `lds_addr` (wave-uniform,
@@ -718,7 +678,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_h2_kernel(
                 const int64_t drow = row + ep.drop_row_base;
                 uint32_t cw = (uint32_t)(lane >> 5);
                 asm volatile("" : "+v"(cw));
-                h2_philox((uint32_t)drow, (uint32_t)(drow >> 32), cw, 0u, seed_k0, seed_k1, r1);
+                philox4x32_10<kPhiloxMulWide>((uint32_t)drow, (uint32_t)(drow >> 32), cw, 0u, seed_k0, seed_k1, r1);
             }
             if (MASKED) {
 #pragma unroll
@@ -742,7 +702,8 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_h2_kernel(
                         //  of the tile loop — spilled registers)
                         uint32_t cw = ((uint32_t)(2 * nb + q) << 1) | (uint32_t)(lane >> 5);
                         asm volatile("" : "+v"(cw));
-                        h2_philox((uint32_t)drow, (uint32_t)(drow >> 32), cw, 0u, k0, k1, r8[q]);
+                        philox4x32_10<kPhiloxMulWide>((uint32_t)drow, (uint32_t)(drow >> 32), cw, 0u, k0, k1,
+                                                      r8[q]);
                     }
                 }
                 // backward mask: the NEXT column block's four 16-byte pieces are requested here,
@@ -1166,7 +1127,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_s16_kernel(
             uint32_t r4[4];
             uint32_t cw = ((uint32_t)cb << 1) | (uint32_t)(q & 1);
             asm volatile("" : "+v"(cw));
-            h2_philox((uint32_t)drow, (uint32_t)(drow >> 32), cw, 0u, seed_k0, seed_k1, r4);
+            philox4x32_10<kPhiloxMulWide>((uint32_t)drow, (uint32_t)(drow >> 32), cw, 0u, seed_k0, seed_k1, r4);
             const uint32_t w0 = (q & 2) ? r4[2] : r4[0], w1 = (q & 2) ? r4[3] : r4[1];
             v.x = (w0 & 0xFFFFu) >= ep.drop_thresh ? v.x * ep.drop_scale : 0.f;
             v.y = (w0 >> 16) >= ep.drop_thresh ? v.y * ep.drop_scale : 0.f;
@@ -1214,7 +1175,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_xw256_s16_kernel(
             const int64_t drow = row + ep.drop_row_base;
             uint32_t cw = (uint32_t)(q & 1);
             asm volatile("" : "+v"(cw));
-            h2_philox((uint32_t)drow, (uint32_t)(drow >> 32), cw, 0u, seed_k0, seed_k1, r1);
+            philox4x32_10<kPhiloxMulWide>((uint32_t)drow, (uint32_t)(drow >> 32), cw, 0u, seed_k0, seed_k1, r1);
         }
         if (MASKED) pmask_row = row >= M ? 0 : (ep.mask_rows != nullptr ? (int64_t)ep.mask_rows[row] : row);
     };
@@ -1578,7 +1539,7 @@ __global__ __launch_bounds__(256, ((K <= 128 && N <= 128) ? ((EPI == 2 || EPI ==
             const int64_t drow = row + ep.drop_row_base;
             uint32_t cw = (uint32_t)h;
             asm volatile("" : "+v"(cw));
-            h2_philox((uint32_t)drow, (uint32_t)(drow >> 32), cw, 0u, seed_k0, seed_k1, r1);
+            philox4x32_10<kPhiloxMulWide>((uint32_t)drow, (uint32_t)(drow >> 32), cw, 0u, seed_k0, seed_k1, r1);
         }
         const __amdgpu_buffer_rsrc_t ys = tile_rsrc(Y, ldy, ldy_b, t, N * 2);
         const uint32_t yoff = (uint32_t)r * ldy_b + 16u * h;
@@ -1616,7 +1577,8 @@ __global__ __launch_bounds__(256, ((K <= 128 && N <= 128) ? ((EPI == 2 || EPI ==
                                 uint32_t cw = ((uint32_t)(2 * nb + (g >> 1)) << 1) | (uint32_t)h;
                                 asm volatile("" : "+v"(cw));       // (no hoisting of the first round)
                                 const int64_t drow = row + ep.drop_row_base;
-                                h2_philox((uint32_t)drow, (uint32_t)(drow >> 32), cw, 0u, k0, k1, r4);
+                                philox4x32_10<kPhiloxMulWide>((uint32_t)drow, (uint32_t)(drow >> 32), cw, 0u,
+                                                              k0, k1, r4);
                             }
                             const uint32_t w0 = (gg & 1) ? r4[2] : r4[0], w1 = (gg & 1) ? r4[3] : r4[1];
                             v[0] = (w0 & 0xFFFFu) >= ep.drop_thresh ? v[0] * ep.drop_scale : 0.f;
@@ -2241,9 +2203,7 @@ int gcn_gemm_xw256_f32(const float *X, int64_t ldx, const float *W, int64_t ldw,
     const int64_t tiles = (M + kTileRows - 1) / kTileRows;
     hipLaunchKernelGGL(gemm_xw256_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, s, X, ldx,
                        (const uint16_t *)workspace, Y, ldy, M);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return gcn_internal_fail_hip((int)e, "gcn_gemm_xw256_f32 launch");
-    return 0;
+    return launched("gcn_gemm_xw256_f32 launch");
 }
 
 size_t gcn_gemm_xw256_h2_workspace_bytes(void)
@@ -2431,9 +2391,7 @@ static int xw256_launch(const char *who, int sch, const float *X, int64_t ldx, c
                         (unsigned)std::min<int64_t>(tiles, kXwGrid), s, X, ldx, x_rows,
                         (const unsigned char *)workspace, x_absmax_bound, Y, ldy, M, (uint32_t *)y_absmax, ep};
     if (!(log_softmax ? XwLogSoftmax::launch(a) : XwKernels::launch(a))) return gcn_internal_fail(GCN_E_BADARG, named(": no kernel for these options"));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return gcn_internal_fail_hip((int)e, named(" launch"));
-    return 0;
+    return launched(named(" launch"));
 }
 
 extern "C" {
@@ -2558,9 +2516,7 @@ int gcn_gemm_xw_bf16(const void *X, int64_t ldx, const void *W, int64_t ldw, voi
     else GCN_LAUNCH_BF16(256, 128);
 #undef GCN_LAUNCH_BF16
 #undef GCN_LAUNCH_BF16_E
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return gcn_internal_fail_hip((int)e, "gcn_gemm_xw_bf16 launch");
-    return 0;
+    return launched("gcn_gemm_xw_bf16 launch");
 }
 
 static int64_t atg_wgs(int64_t n_list)
@@ -2629,9 +2585,7 @@ static int atg256_launch(int sch, const float *A, int64_t lda, const int32_t *ro
     if (colsum_g != nullptr)
         hipLaunchKernelGGL(atg_colsum_reduce_kernel, dim3(1), dim3(256), 0, s, (const float *)cs_partial, (int)n_wg,
                            colsum_g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return gcn_internal_fail_hip((int)e, "gcn_gemm_atg256_f32 launch");
-    return 0;
+    return launched("gcn_gemm_atg256_f32 launch");
 }
 
 extern "C" {
@@ -2702,9 +2656,7 @@ int gcn_gemm_atg_bf16(const void *A, int64_t lda, const int32_t *rows_a, const v
                        lda, rows_a, (const uint16_t *)G, ldg, rows_g, n_list, (float *)workspace, per);
     hipLaunchKernelGGL(atg_reduce_kernel_n, dim3(128 * 128 / 256), dim3(256), 0, s,
                        (const float *)workspace, (int)n_wg, out, ldo, 128, 128 * 128);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return gcn_internal_fail_hip((int)e, "gcn_gemm_atg_bf16 launch");
-    return 0;
+    return launched("gcn_gemm_atg_bf16 launch");
 }
 
 }   // extern "C"

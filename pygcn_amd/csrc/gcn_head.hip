@@ -49,11 +49,9 @@
 #include <cstdio>
 
 #include "gcn_spmm.h"
+#include "gcn_internal.h"
 
 #pragma clang fp contract(off)
-
-int gcn_internal_fail(int code, const char *msg);
-int gcn_internal_fail_hip(int hip_error, const char *where);
 
 namespace {
 
@@ -76,9 +74,6 @@ struct Params {
     int64_t n, ldx;
     int C, T, d, H1, H2, rows_per_block;
 };
-
-// a / D for 0 <= a < 2^13 and 1 <= D <= 2^13 given r = 1.0f / D (gcn_eval.hip: the truncation is exact)
-__device__ __forceinline__ int fdiv(int a, float r) { return (int)(((float)a + 0.5f) * r); }
 
 // LDS traffic of a wave's OWN tiles: program order within the wave is enough, no workgroup barrier
 __device__ __forceinline__ void wave_sync()
@@ -739,13 +734,6 @@ struct Shape {
     }
 };
 
-int bad(const char *who, int code, const char *what)
-{
-    char msg[200];
-    std::snprintf(msg, sizeof msg, "%s: %s", who, what);
-    return gcn_internal_fail(code, msg);
-}
-
 bool off(const void *ptr, uintptr_t a) { return (uintptr_t)ptr % a != 0; }
 
 template <int HP, int MODE>
@@ -803,12 +791,6 @@ int check_args(const char *who, const float *h, const float *x, int64_t ldx, int
         return bad(who, GCN_E_WORKSPACE, "workspace too small");
     if (off(workspace, 16)) return bad(who, GCN_E_ALIGN, "16-byte alignment required");
     return 0;
-}
-
-int launched(const char *who, hipError_t e)
-{
-    if (e == hipSuccess) e = hipGetLastError();
-    return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, who);
 }
 
 }  // namespace

@@ -17,10 +17,7 @@
 #include <cstdio>
 
 #include "gcn_spmm.h"
-
-// error reporting shared with gcn_spmm.hip (one gcn_last_error() for the whole library)
-int gcn_internal_fail(int code, const char *msg);
-int gcn_internal_fail_hip(int hip_error, const char *where);
+#include "gcn_internal.h"
 
 namespace {
 
@@ -265,9 +262,7 @@ int gcn_csr_transpose_device(const void *rowptr, int rowptr_is64, const int32_t 
     else
         hipLaunchKernelGGL(unpack_entries_kernel<int32_t>, dim3(blocks), dim3(256), 0, s, pay_out,
                            keys_sorted, n_cols, nnz, (int32_t *)rowptr_t, col_t, val_t);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ifail_hip(e, "gcn_csr_transpose_device: launch");
-    return 0;
+    return launched("gcn_csr_transpose_device: launch");
 }
 
 size_t gcn_coo_to_csr_workspace_bytes(int64_t n_rows, int64_t n_cols, int64_t nnz)
@@ -332,9 +327,7 @@ int gcn_coo_to_csr_device(const int64_t *row, const int64_t *col, const float *v
         hipLaunchKernelGGL(coo_reduce_kernel<int32_t>, dim3(blocks), dim3(256), 0, s, key_sorted,
                            pos_sorted, outpos, val, nnz, n_rows, n_cols, reduce == GCN_REDUCE_MAX,
                            (int32_t *)rowptr_out, col_out, val_out, nnz_out);
-    e = hipGetLastError();
-    if (e != hipSuccess) return ifail_hip(e, "gcn_coo_to_csr_device: launch");
-    return 0;
+    return launched("gcn_coo_to_csr_device: launch");
 }
 
 int gcn_row_normalize_device(const void *rowptr, int rowptr_is64, float *val, int64_t n_rows,
@@ -352,9 +345,7 @@ int gcn_row_normalize_device(const void *rowptr, int rowptr_is64, float *val, in
     else
         hipLaunchKernelGGL(row_normalize_kernel<int32_t>, dim3(blocks), dim3(256), 0, s,
                            (const int32_t *)rowptr, val, n_rows);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ifail_hip(e, "gcn_row_normalize_device: launch");
-    return 0;
+    return launched("gcn_row_normalize_device: launch");
 }
 
 }   // extern "C"

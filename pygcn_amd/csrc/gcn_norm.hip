@@ -77,59 +77,9 @@
 #include <cstdio>
 
 #include "gcn_spmm.h"
-
-int gcn_internal_fail(int code, const char *msg);
-int gcn_internal_fail_hip(int hip_error, const char *where);
+#include "gcn_internal.h"
 
 namespace {
-
-typedef uint16_t bf16_t;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-template <typename T> struct Lane;       // 16 bytes of a row <-> V floats
-template <> struct Lane<float> {
-    static constexpr int V = 4;
-    typedef f32x4 Raw;
-    static __device__ __forceinline__ void unpack(const Raw &r, float (&x)[4])
-    {
-        x[0] = r.x; x[1] = r.y; x[2] = r.z; x[3] = r.w;
-    }
-    static __device__ __forceinline__ Raw pack(const float (&x)[4])
-    {
-        Raw r = {x[0], x[1], x[2], x[3]};
-        return r;
-    }
-};
-template <> struct Lane<bf16_t> {
-    static constexpr int V = 8;
-    typedef u32x4 Raw;
-    static __device__ __forceinline__ void unpack(const Raw &r, float (&x)[8])
-    {
-        const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            x[2 * i] = __uint_as_float(w[i] << 16);
-            x[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-        }
-    }
-    static __device__ __forceinline__ uint32_t pair(float lo, float hi)
-    {
-        f32x2 v = {lo, hi};
-        bf16x2 b = __builtin_convertvector(v, bf16x2);   // v_cvt_pk_bf16_f32, round-to-nearest-even
-        return __builtin_bit_cast(uint32_t, b);
-    }
-    static __device__ __forceinline__ Raw pack(const float (&x)[8])
-    {
-        Raw r = {pair(x[0], x[1]), pair(x[2], x[3]), pair(x[4], x[5]), pair(x[6], x[7])};
-        return r;
-    }
-};
-
-// torch.relu: NaN stays NaN (fmaxf would drop it)
-__device__ __forceinline__ float act(float z, int relu) { return (relu && z < 0.f) ? 0.f : z; }
 
 // where a thread stands in its block's slab, and the slab in the matrix: blockIdx.y is the column
 // window [w0, w0 + F) of a [n_rows, gridDim.y * F] matrix (one window, pitch F: the 2-D entry points)
@@ -602,13 +552,6 @@ bool shape_ok(int64_t n_rows, int64_t F, int dtype)
 
 bool batch_ok(int64_t batch) { return batch >= 1 && batch <= kMaxBatch; }
 
-int bad(const char *who, int code, const char *what)
-{
-    char msg[200];
-    std::snprintf(msg, sizeof msg, "%s: %s", who, what);
-    return gcn_internal_fail(code, msg);
-}
-
 // the argument checks every BatchNorm entry point shares; 0 = go on
 int check(const char *who, int dtype, int64_t n_rows, int64_t F, int64_t batch, bool null_ptr, uintptr_t tensors)
 {
@@ -634,12 +577,6 @@ int check_pool(const char *who, int dtype, int64_t n_rows, int64_t C, int64_t ba
     if (null_ptr) return bad(who, GCN_E_BADARG, "NULL pointer");
     if (tensors % 16 != 0) return bad(who, GCN_E_ALIGN, "16-byte alignment required");
     return 0;
-}
-
-int launched(const char *who)
-{
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, who);
 }
 
 dim3 finish_grid(int64_t F, int64_t batch) { return dim3((unsigned)((F + 31) / 32), (unsigned)batch); }

@@ -61,14 +61,9 @@
 #include <cstdio>
 
 #include "gcn_spmm.h"
-
-int gcn_internal_fail(int code, const char *msg);
-int gcn_internal_fail_hip(int hip_error, const char *where);
+#include "gcn_internal.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kF = 32;                    // the one width built
 constexpr int kWaves = 4;                 // per block
@@ -76,9 +71,6 @@ constexpr int kThreads = 64 * kWaves;
 constexpr int64_t kMaxBlocks = 512;
 constexpr int kRow = kF * kF + 4 * kF;    // doubles per partial row: P[32][32], sum dy, sum dy t, sum t, sum t^2
 constexpr int64_t kMaxBatch = 65535;      // windows ride on gridDim.y
-
-// torch.relu: NaN stays NaN
-__device__ __forceinline__ float act(float z, int relu) { return (relu && z < 0.f) ? 0.f : z; }
 
 // (x - mean) * rstd, rounded after the subtraction and after the product (bn_apply_kernel's expression)
 __device__ __forceinline__ float normalised(float x, float mu, float rs)
@@ -355,13 +347,6 @@ bool shape_ok(int64_t n_rows, int64_t Fin, int64_t Fout, int64_t batch)
            batch <= kMaxBatch;
 }
 
-int bad(const char *who, int code, const char *what)
-{
-    char msg[200];
-    std::snprintf(msg, sizeof msg, "%s: %s", who, what);
-    return gcn_internal_fail(code, msg);
-}
-
 int check(const char *who, int64_t n_rows, int64_t Fin, int64_t Fout, int64_t batch, bool null_ptr,
           uintptr_t tensors, uintptr_t doubles)
 {
@@ -371,12 +356,6 @@ int check(const char *who, int64_t n_rows, int64_t Fin, int64_t Fout, int64_t ba
     if (tensors % 16 != 0 || doubles % 8 != 0)
         return bad(who, GCN_E_ALIGN, "16-byte alignment required (coef: 8)");
     return 0;
-}
-
-int launched(const char *who)
-{
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, who);
 }
 
 }   // namespace

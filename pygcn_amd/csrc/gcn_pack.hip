@@ -20,15 +20,12 @@
 #include <cstdint>
 
 #include "gcn_spmm.h"
-
-int gcn_internal_fail(int code, const char *msg);
-int gcn_internal_fail_hip(int hip_error, const char *where);
+#include "gcn_internal.h"
 
 namespace {
 
 constexpr int kWave = 64;
 constexpr int kRowsPerBlock = 4;          // one wave per row, 4 waves per workgroup
-typedef uint16_t bf16_t;
 
 template <typename T> struct Quad;       // 4 consecutive elements of a row <-> 4 floats
 template <> struct Quad<float> {
@@ -65,17 +62,12 @@ __device__ __forceinline__ int below(unsigned long long m)      // set bits of m
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
-template <int CTRL> __device__ __forceinline__ uint32_t dpp_u(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true);
-}
-
 // OR over each group of 8 consecutive lanes (quad xor-1, xor-2, then the half-row mirror)
 __device__ __forceinline__ uint32_t or8(uint32_t v)
 {
-    v |= dpp_u<0xB1>(v);
-    v |= dpp_u<0x4E>(v);
-    v |= dpp_u<0x141>(v);
+    v |= dpp_move<0xB1>(v);
+    v |= dpp_move<0x4E>(v);
+    v |= dpp_move<0x141>(v);
     return v;
 }
 
@@ -215,7 +207,7 @@ constexpr int kPack512Cap = GCN_PACK512_CAPACITY;
 __device__ __forceinline__ uint32_t or16(uint32_t v)       // OR over each row of 16 lanes
 {
     v = or8(v);
-    v |= dpp_u<0x140>(v);
+    v |= dpp_move<0x140>(v);
     return v;
 }
 
@@ -305,8 +297,7 @@ int gcn_rows_pack_count(int dtype, const void *src, int64_t ld, const int64_t *r
         hipLaunchKernelGGL(pack_count_kernel<float>, grid, block, 0, s, (const float *)src, ld, rows, m, (int)F, bits, counts);
     else
         hipLaunchKernelGGL(pack_count_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)src, ld, rows, m, (int)F, bits, counts);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, "gcn_rows_pack_count launch");
+    return launched("gcn_rows_pack_count launch");
 }
 
 int gcn_rows_pack_values(int dtype, const void *src, int64_t ld, const int64_t *rows, int64_t m, int64_t F,
@@ -324,8 +315,7 @@ int gcn_rows_pack_values(int dtype, const void *src, int64_t ld, const int64_t *
         hipLaunchKernelGGL(pack_values_kernel<float>, grid, block, 0, s, (const float *)src, ld, rows, m, (int)F, offsets, (float *)vals);
     else
         hipLaunchKernelGGL(pack_values_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)src, ld, rows, m, (int)F, offsets, (bf16_t *)vals);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, "gcn_rows_pack_values launch");
+    return launched("gcn_rows_pack_values launch");
 }
 
 int gcn_rows_unpack(int dtype, const uint32_t *bits, const int64_t *offsets, const void *vals, int64_t m,
@@ -343,8 +333,7 @@ int gcn_rows_unpack(int dtype, const uint32_t *bits, const int64_t *offsets, con
         hipLaunchKernelGGL(unpack_kernel<float>, grid, block, 0, s, bits, offsets, (const float *)vals, m, (int)F, (float *)dst, ldd);
     else
         hipLaunchKernelGGL(unpack_kernel<bf16_t>, grid, block, 0, s, bits, offsets, (const bf16_t *)vals, m, (int)F, (bf16_t *)dst, ldd);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, "gcn_rows_unpack launch");
+    return launched("gcn_rows_unpack launch");
 }
 
 int gcn_rows_pack512(const float *src, int64_t ld, int64_t m, uint32_t *slots, void *stream)
@@ -358,8 +347,7 @@ int gcn_rows_pack512(const float *src, int64_t ld, int64_t m, uint32_t *slots, v
     if (blocks > INT32_MAX) return gcn_internal_fail(GCN_E_BADARG, "gcn_rows_pack512: too many rows");
     const dim3 grid((unsigned)blocks), block(kWave * kRowsPerBlock);
     hipLaunchKernelGGL(pack512_kernel, grid, block, 0, (hipStream_t)stream, src, ld, m, slots);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, "gcn_rows_pack512 launch");
+    return launched("gcn_rows_pack512 launch");
 }
 
 int gcn_bits_row_counts(const uint32_t *bits, int64_t m, int64_t words, int32_t *counts, void *stream)
@@ -370,8 +358,7 @@ int gcn_bits_row_counts(const uint32_t *bits, int64_t m, int64_t words, int32_t 
     if (bits == nullptr || counts == nullptr) return gcn_internal_fail(GCN_E_BADARG, "gcn_bits_row_counts: NULL pointer");
     const dim3 grid((unsigned)((m * 8 + 255) / 256)), block(256);
     hipLaunchKernelGGL(bits_count_kernel, grid, block, 0, (hipStream_t)stream, bits, m, (int)words, counts);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, "gcn_bits_row_counts launch");
+    return launched("gcn_bits_row_counts launch");
 }
 
 }   // extern "C"

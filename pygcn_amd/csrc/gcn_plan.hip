@@ -28,9 +28,7 @@
 #include <cstdint>
 
 #include "gcn_spmm.h"
-
-int gcn_internal_fail(int code, const char *msg);
-int gcn_internal_fail_hip(int hip_error, const char *where);
+#include "gcn_internal.h"
 
 namespace {
 
@@ -266,9 +264,7 @@ int gcn_plan_count_device(const void *rowptr, int rowptr_is64, int64_t n_rows, i
     e = hipcub::DeviceScan::ExclusiveSum(ws.scan_temp, tb, ws.mark, ws.item_id, m, s);
     if (e != hipSuccess) return gcn_internal_fail_hip((int)e, "gcn_plan_count_device: scan");
     hipLaunchKernelGGL(plan_counts_kernel, dim3(1), dim3(64), 0, s, ws, n_rows, counts);
-    e = hipGetLastError();
-    if (e != hipSuccess) return gcn_internal_fail_hip((int)e, "gcn_plan_count_device: launch");
-    return 0;
+    return launched("gcn_plan_count_device: launch");
 }
 
 int gcn_plan_fill_device(const void *rowptr, int rowptr_is64, int64_t n_rows, int32_t long_thresh,
@@ -296,9 +292,7 @@ int gcn_plan_fill_device(const void *rowptr, int rowptr_is64, int64_t n_rows, in
         hipLaunchKernelGGL(plan_fill_kernel<int32_t>, grid, block, 0, s, (const int32_t *)rowptr, n_rows,
                            long_thresh, ws, items, n_items, chunk_row, chunk_e0, n_chunks, long_row,
                            long_chunk0, n_long);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return gcn_internal_fail_hip((int)e, "gcn_plan_fill_device: launch");
-    return 0;
+    return launched("gcn_plan_fill_device: launch");
 }
 
 }   // extern "C"

@@ -7,13 +7,12 @@
 //                       compact pass draws the mask the full-height pass draws at the same seed.
 //   gcn_csr_take_rows   rows of a CSR matrix as a CSR matrix of their own, columns optionally renumbered.
 //
-// Dropout.  A Philox call yields 128 bits, and every call made here serves ALL the columns it covers:
-//   T != 32768  eight 16-bit fields: call `blk` of a row covers the columns {16c + 4b + (0..3),
-//               16c + 4b + 8 + (0..3)}, blk = 2c + b.  One thread per (row, blk): two runs of four
-//               consecutive elements; consecutive lanes take consecutive blk, so the first accesses of a
-//               wave cover the lower halves of its 64-byte groups and the second the upper halves.
-//   T == 32768  128 one-bit fields: call (s, b) of a row covers the columns of the 256-column span s whose
-//               bit 2 equals b.  A workgroup of 256 threads takes 128 rows of one span: thread t draws the
+// Dropout.  The keep function (block, field, one-bit form) is specified in gcn_internal.h above
+// philox4x32_10; every call made here serves ALL the columns it covers:
+//   T != 32768  one thread per (row, block): two runs of four consecutive elements; consecutive lanes take
+//               consecutive blocks, so the first accesses of a wave cover the lower halves of its 64-byte
+//               groups and the second the upper halves.
+//   T == 32768  a workgroup of 256 threads takes 128 rows of one 256-column span s: thread t draws the
 //               call (row t >> 1, b = t & 1) into LDS, then the workgroup sweeps the 128 x 256 window four
 //               rows at a time, a wave per row and four consecutive columns per lane (one 16-byte access at
 //               fp32), each lane picking its four bits out of LDS.
@@ -28,43 +27,12 @@
 #include <cstdint>
 
 #include "gcn_spmm.h"
-
-int gcn_internal_fail(int code, const char *msg);
-int gcn_internal_fail_hip(int hip_error, const char *where);
+#include "gcn_internal.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kBitRows = kBlock / 2;      // rows of one workgroup of the one-bit form
-typedef uint16_t bf16_t;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-// threshold and scale of the header's dropout rule (struct gcn_epilogue): T = clamp(round(p * 65536), 1,
-// 65535), s = 65536 / (65536 - T)
-uint32_t dropout_threshold16(float p)
-{
-    if (!(p > 0.f)) return 0u;
-    const double t = (double)p * 65536.0 + 0.5;
-    return (uint32_t)std::min(65535.0, std::max(1.0, (double)(int64_t)t));
-}
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                              uint32_t k0, uint32_t k1, uint32_t (&out)[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 template <typename T> struct Run4;       // four consecutive elements of a row <-> four floats
 template <> struct Run4<float> {
@@ -80,12 +48,6 @@ template <> struct Run4<float> {
     static __device__ __forceinline__ float get(const float *p) { return *p; }
     static __device__ __forceinline__ void put(float *p, float x) { *p = x; }
 };
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi)
-{
-    f32x2 v = {lo, hi};
-    bf16x2 b = __builtin_convertvector(v, bf16x2);    // round-to-nearest-even
-    return __builtin_bit_cast(uint32_t, b);
-}
 template <> struct Run4<bf16_t> {
     static __device__ __forceinline__ void load(const bf16_t *p, float (&x)[4])
     {
@@ -156,7 +118,7 @@ __global__ __launch_bounds__(kBlock) void dropout_rows_fields_kernel(T *__restri
         if (f0 >= p.F) continue;
         const int64_t row = (p.rows != nullptr ? p.rows[r] : r) + p.row_base;
         uint32_t w[4];
-        philox4x32_10((uint32_t)row, (uint32_t)((uint64_t)row >> 32), blk, 0u, k0, k1, w);
+        philox4x32_10<kPhiloxMulPair>((uint32_t)row, (uint32_t)((uint64_t)row >> 32), blk, 0u, k0, k1, w);
         T *base = h + r * p.ld;
 #pragma unroll
         for (int half = 0; half < 2; ++half) {      // fields 0..3 = columns f0 + (0..3), 4..7 = f0 + 8 + (0..3)
@@ -185,7 +147,8 @@ __global__ __launch_bounds__(kBlock) void dropout_rows_bits_kernel(T *__restrict
         if (r < p.m) {
             const int64_t row = (p.rows != nullptr ? p.rows[r] : r) + p.row_base;
             uint32_t w[4];
-            philox4x32_10((uint32_t)row, (uint32_t)((uint64_t)row >> 32), (span << 1) | (uint32_t)(t & 1), 0u, k0, k1, w);
+            philox4x32_10<kPhiloxMulPair>((uint32_t)row, (uint32_t)((uint64_t)row >> 32),
+                                          (span << 1) | (uint32_t)(t & 1), 0u, k0, k1, w);
 #pragma unroll
             for (int j = 0; j < 4; ++j) bits[t][j] = w[j];
         }
@@ -268,8 +231,8 @@ int gcn_dropout_rows(int dtype, void *h, int64_t ld, const int64_t *rows, int64_
     DropParams p;
     p.rows = rows; p.m = m; p.F = F; p.ld = ld; p.row_base = drop_row_base;
     p.seed_dev = seed_dev; p.seed_lo = (uint32_t)seed; p.seed_hi = (uint32_t)(seed >> 32);
-    p.thresh = dropout_threshold16(dropout_p);
-    p.scale = 65536.f / (float)(65536u - p.thresh);
+    p.thresh = gcn_dropout_threshold16(dropout_p);
+    p.scale = gcn_dropout_scale16(p.thresh);
     p.vec = (((uintptr_t)h) % (4 * esize) == 0 && ld % 4 == 0) ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
     if (p.thresh == 32768u) {
@@ -292,8 +255,7 @@ int gcn_dropout_rows(int dtype, void *h, int64_t ld, const int64_t *rows, int64_
         else
             hipLaunchKernelGGL(dropout_rows_fields_kernel<bf16_t>, grid, block, 0, s, (bf16_t *)h, p);
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, "gcn_dropout_rows launch");
+    return launched("gcn_dropout_rows launch");
 }
 
 int gcn_csr_take_rows(const void *rowptr, int rowptr_is64, const int32_t *col, const float *val, const int64_t *rows,
@@ -316,8 +278,7 @@ int gcn_csr_take_rows(const void *rowptr, int rowptr_is64, const int32_t *col, c
         if (out_is64) GCN_TAKE(int32_t, int64_t); else GCN_TAKE(int32_t, int32_t);
     }
 #undef GCN_TAKE
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, "gcn_csr_take_rows launch");
+    return launched("gcn_csr_take_rows launch");
 }
 
 }   // extern "C"

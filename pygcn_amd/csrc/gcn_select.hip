@@ -45,9 +45,7 @@
 #include <cstdio>
 
 #include "gcn_spmm.h"
-
-int gcn_internal_fail(int code, const char *msg);
-int gcn_internal_fail_hip(int hip_error, const char *where);
+#include "gcn_internal.h"
 
 namespace {
 
@@ -350,25 +348,7 @@ __global__ __launch_bounds__(256) void topk_flag_kernel(const float *s, const fl
     }
 }
 
-// the rounds of gcn_spmm.hip's dropout generator
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                              uint32_t k1, uint32_t (&out)[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// a thread draws the four vertices 4q .. 4q + 3 of its window from one Philox call
+// a thread draws the four vertices 4q .. 4q + 3 of its window from one call of the dropout's generator
 __global__ __launch_bounds__(256) void race_keys_kernel(const float *p, float *keys, int64_t n_rows,
                                                         uint32_t seed_lo, uint32_t seed_hi)
 {
@@ -376,7 +356,8 @@ __global__ __launch_bounds__(256) void race_keys_kernel(const float *p, float *k
     const int64_t groups = (n_rows + 3) >> 2;
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < groups; q += (int64_t)gridDim.x * 256) {
         uint32_t u[4];
-        philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), (uint32_t)blockIdx.y, 1u, seed_lo, seed_hi, u);
+        philox4x32_10<kPhiloxMulPair>((uint32_t)q, (uint32_t)(q >> 32), (uint32_t)blockIdx.y, 1u, seed_lo, seed_hi,
+                                      u);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int64_t r = 4 * q + i;
@@ -386,19 +367,6 @@ __global__ __launch_bounds__(256) void race_keys_kernel(const float *p, float *k
             }
         }
     }
-}
-
-int bad(const char *who, int code, const char *what)
-{
-    char msg[200];
-    std::snprintf(msg, sizeof msg, "%s: %s", who, what);
-    return gcn_internal_fail(code, msg);
-}
-
-int launched(const char *who)
-{
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, who);
 }
 
 bool rows_ok(int64_t n_rows) { return n_rows >= 1 && n_rows <= kMaxRows; }

@@ -30,22 +30,7 @@
 #include <type_traits>
 
 #include "gcn_spmm.h"
-
-// keep-threshold of the fused dropout: an element is kept iff its 16-bit field >= round(p * 2^16),
-// clamped to [1, 65535] for p > 0 (0 = dropout off) — include/gcn_spmm.h, struct gcn_epilogue
-static inline uint32_t gcn_dropout_threshold16(float p)
-{
-    if (!(p > 0.f)) return 0u;
-    const double t = (double)p * 65536.0 + 0.5;
-    return (uint32_t)std::min(65535.0, std::max(1.0, (double)(int64_t)t));
-}
-// the scale that goes with that threshold: the kernels keep an element with probability
-// (65536 - T) / 65536, so 65536 / (65536 - T) — not 1 / (1 - p) of the unquantised p — makes
-// E[dropout(x)] = x exactly (the two agree to 2^-17 away from the clamps, and exactly at p = 1/2)
-static inline float gcn_dropout_scale16(uint32_t thresh)
-{
-    return thresh == 0u ? 1.f : 65536.f / (float)(65536u - thresh);
-}
+#include "gcn_internal.h"
 
 namespace {
 
@@ -111,55 +96,14 @@ struct KParams {
 // ------------------------------------------------------------------------------------------
 // element traits: how VEC elements of T travel between memory and fp32 registers
 // ------------------------------------------------------------------------------------------
-typedef uint16_t bf16_t;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
+// Elem<T, VEC>: the 16-byte forms are gcn_internal.h's Lane<T>; the scalar forms serve the narrow kernels only
 template <typename T, int VEC> struct Elem;
-
-template <> struct Elem<float, 4> {
-    typedef f32x4 Raw;
-    static __device__ __forceinline__ void unpack(const Raw &r, float (&x)[4])
-    {
-        x[0] = r.x; x[1] = r.y; x[2] = r.z; x[3] = r.w;
-    }
-    static __device__ __forceinline__ Raw pack(const float (&x)[4])
-    {
-        Raw r = {x[0], x[1], x[2], x[3]};
-        return r;
-    }
-};
+template <> struct Elem<float, 4> : Lane<float> {};
+template <> struct Elem<bf16_t, 8> : Lane<bf16_t> {};
 template <> struct Elem<float, 1> {
     typedef float Raw;
     static __device__ __forceinline__ void unpack(const Raw &r, float (&x)[1]) { x[0] = r; }
     static __device__ __forceinline__ Raw pack(const float (&x)[1]) { return x[0]; }
-};
-
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi)
-{
-    f32x2 v = {lo, hi};
-    bf16x2 b = __builtin_convertvector(v, bf16x2);   // v_cvt_pk_bf16_f32, round-to-nearest-even
-    return __builtin_bit_cast(uint32_t, b);
-}
-template <> struct Elem<bf16_t, 8> {
-    typedef u32x4 Raw;
-    static __device__ __forceinline__ void unpack(const Raw &r, float (&x)[8])
-    {
-        const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            x[2 * i] = __uint_as_float(w[i] << 16);
-            x[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-        }
-    }
-    static __device__ __forceinline__ Raw pack(const float (&x)[8])
-    {
-        Raw r = {pack_bf16x2(x[0], x[1]), pack_bf16x2(x[2], x[3]), pack_bf16x2(x[4], x[5]),
-                 pack_bf16x2(x[6], x[7])};
-        return r;
-    }
 };
 template <> struct Elem<bf16_t, 1> {
     typedef bf16_t Raw;
@@ -196,35 +140,8 @@ __device__ __forceinline__ float readlane_f(float v, int l)
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
 
-// Philox4x32-10 (Salmon et al., SC'11): counter-based, so the dropout mask of element (row, f)
-// depends only on (seed, row, f) — never on which kernel variant, vector width, wave or launch
-// produced the row.  One call yields 128 bits = EIGHT 16-bit keep fields (ABI 22; before: four
-// 32-bit words — half the integer multiplies per element now) — or, at p = 1/2 where one bit
-// decides, 128 ONE-bit fields (ABI 23, see apply_dropout).  Element (row, f), 16-bit form:
-//     block = ((f >> 4) << 1) | ((f >> 2) & 1)          counter word 2
-//     field = (((f >> 3) & 1) << 2) | (f & 3)           0..7: word field >> 1, half field & 1
-//     w     = philox(counter = (row_lo, row_hi, block, 0), key = seed)   (row incl. drop_row_base)
-//     keep  = ((w[field >> 1] >> 16 * (field & 1)) & 0xFFFF) >= round(p * 65536)
-// The block groups columns {16c + 4b + (0..3), 16c + 4b + 8 + (0..3)} (b = bit 2 of f): exactly the
-// eight columns one lane of the MFMA GEMMs' transposed accumulator tile stores per 16-column
-// group (gcn_gemm.hip), so the GEMM epilogues need ONE call per eight stored elements too.
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                              uint32_t k0, uint32_t k1, uint32_t (&out)[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
+// the keep function (gcn_internal.h, above philox4x32_10) of VEC consecutive columns from f on:
+// VEC = 1, or VEC and f multiples of 4
 template <int VEC>
 __device__ __forceinline__ void apply_dropout(const KParams &p, int64_t row, int f, float (&o)[VEC])
 {
@@ -237,17 +154,13 @@ __device__ __forceinline__ void apply_dropout(const KParams &p, int64_t row, int
     }
     row += p.drop_row_base;
     if (p.drop_thresh == 32768u) {
-        // p = 1/2 (the reference's default): ONE bit decides, a call yields 128 one-bit fields —
-        //     block = ((f >> 8) << 1) | ((f >> 2) & 1),   index = (((f & 255) >> 3) << 2) | (f & 3)
-        //     keep  = (w[index >> 5] >> (index & 31)) & 1
-        // the same layout rule at a 256-column span: a lane of the GEMMs' transposed accumulator
-        // tile finds ALL its columns of a 256-wide row in one call (16 calls per tile before).
+        // p = 1/2 (the reference's default): the one-bit form, 128 fields per call
 #pragma unroll
         for (int q = 0; q < (VEC + 3) / 4; ++q) {
             const int fq = f + 4 * q;
             const uint32_t blk = ((uint32_t)(fq >> 8) << 1) | ((uint32_t)(fq >> 2) & 1u);
             const int idx = (((fq & 255) >> 3) << 2) | (fq & 3);          // (VEC >= 4: fq & 3 == 0)
-            philox4x32_10((uint32_t)row, (uint32_t)(row >> 32), blk, 0u, k0, k1, r);
+            philox4x32_10<kPhiloxMulPair>((uint32_t)row, (uint32_t)(row >> 32), blk, 0u, k0, k1, r);
             const int ws = idx >> 5;
             const uint32_t w = (ws & 2) ? ((ws & 1) ? r[3] : r[2]) : ((ws & 1) ? r[1] : r[0]);
             const uint32_t nib = w >> (idx & 31);
@@ -260,7 +173,7 @@ __device__ __forceinline__ void apply_dropout(const KParams &p, int64_t row, int
     if (VEC == 1) {
         const uint32_t blk = ((uint32_t)(f >> 4) << 1) | ((uint32_t)(f >> 2) & 1u);
         const int fld = (((f >> 3) & 1) << 2) | (f & 3);
-        philox4x32_10((uint32_t)row, (uint32_t)(row >> 32), blk, 0u, k0, k1, r);
+        philox4x32_10<kPhiloxMulPair>((uint32_t)row, (uint32_t)(row >> 32), blk, 0u, k0, k1, r);
         const uint32_t w = (fld & 4) ? ((fld & 2) ? r[3] : r[2]) : ((fld & 2) ? r[1] : r[0]);
         const uint32_t bits = (fld & 1) ? (w >> 16) : (w & 0xFFFFu);
         o[0] = (bits >= p.drop_thresh) ? o[0] * p.drop_scale : 0.f;
@@ -269,7 +182,7 @@ __device__ __forceinline__ void apply_dropout(const KParams &p, int64_t row, int
         for (int q = 0; q < VEC / 4; ++q) {       // 4 consecutive columns = fields 4s .. 4s+3 of one block
             const int fq = f + 4 * q;
             const uint32_t blk = ((uint32_t)(fq >> 4) << 1) | ((uint32_t)(fq >> 2) & 1u);
-            philox4x32_10((uint32_t)row, (uint32_t)(row >> 32), blk, 0u, k0, k1, r);
+            philox4x32_10<kPhiloxMulPair>((uint32_t)row, (uint32_t)(row >> 32), blk, 0u, k0, k1, r);
             const bool hi = ((fq >> 3) & 1) != 0;
             const uint32_t w0 = hi ? r[2] : r[0], w1 = hi ? r[3] : r[1];
             o[4 * q + 0] = ((w0 & 0xFFFFu) >= p.drop_thresh) ? o[4 * q + 0] * p.drop_scale : 0.f;
@@ -281,17 +194,9 @@ __device__ __forceinline__ void apply_dropout(const KParams &p, int64_t row, int
 }
 
 // xor-butterfly reductions inside groups of LPR consecutive lanes (LPR a power of two).  The first
-// four steps are DPP row operations — VALU modifiers, no trip through the LDS crossbar and no
-// address registers: quad_perm [1,0,3,2] and [2,3,0,1] are the xor-1 / xor-2 exchanges; after them
-// a quad is uniform, so row_half_mirror (lane i <-> 7 - i) and row_mirror (i <-> 15 - i) act as
-// xor 4 / xor 8.  max and + are commutative, so every lane of a group ends with the same bits.
+// four steps are DPP row operations (dpp_move, gcn_internal.h): xor 1, 2, 4, 8.  max and + are
+// commutative, so every lane of a group ends with the same bits.
 // Wider groups finish with wave shuffles (ds_bpermute).
-template <int CTRL>
-__device__ __forceinline__ float dpp_move(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-
 template <int LPR>
 __device__ __forceinline__ float group_max(float m)
 {
@@ -1497,14 +1402,12 @@ int spmm_typed(const gcn_csr_plan *plan, KParams &kp, hipStream_t s)
             dim3 grid(nblk, (unsigned)((F + lpr - 1) / lpr));
             launch_narrow_lpr<T, 1>(kp, is64, lpr, grid, s);
         }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail_hip(e, "spmm launch");
+        if (int rc = launched("spmm launch")) return rc;
     }
     if (kp.n_long > 0) {
         hipLaunchKernelGGL((spmm_long_reduce_kernel<T>), dim3((unsigned)((kp.n_long + 3) / 4)), dim3(256), 0,
                            s, kp);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail_hip(e, "long-row reduce launch");
+        return launched("long-row reduce launch");
     }
     return 0;
 }
@@ -1654,7 +1557,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void sddmm_kernel(SddmmParam
 
 }   // namespace
 
-// shared with gcn_ingest.hip
+// shared with the other .hip files (declared in gcn_internal.h)
 int gcn_internal_fail(int code, const char *msg) { return fail(code, msg); }
 int gcn_internal_fail_hip(int hip_error, const char *where)
 {
@@ -1856,9 +1759,7 @@ int gcn_relu_dropout_backward(int dtype, const void *grad_out, const void *out, 
                                (const bf16_t *)grad_out, (const bf16_t *)out, (bf16_t *)grad_pre,
                                n_units, scale);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "relu_dropout_backward launch");
-    return 0;
+    return launched("relu_dropout_backward launch");
 }
 
 static constexpr int64_t kColsumBlocks = 2048;   // slabs of rows = partial column sums
@@ -1945,9 +1846,7 @@ static int bwd_colsum_impl(const char *who, int mode, int dtype, const void *gra
     if (row_bits != nullptr)
         hipLaunchKernelGGL(pack_row_flags_kernel, dim3((unsigned)((((n_rows + 31) >> 5) + 255) / 256)),
                            dim3(256), 0, s, (const uint8_t *)row_nonzero, row_bits, n_rows);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, who);
-    return 0;
+    return launched(who);
 }
 
 int gcn_relu_dropout_backward_colsum(int dtype, const void *grad_out, const void *out, void *grad_pre,
@@ -2035,9 +1934,7 @@ int gcn_sddmm_csr(const gcn_csr_plan *plan, int dtype, const void *G, int64_t ld
         else GCN_LAUNCH_SDDMM(bf16_t, 1);
     }
 #undef GCN_LAUNCH_SDDMM
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "gcn_sddmm_csr launch");
-    return 0;
+    return launched("gcn_sddmm_csr launch");
 }
 
 int gcn_csr_transpose_host(const void *rowptr_host, int rowptr_is64, const int32_t *col,

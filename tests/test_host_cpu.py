@@ -401,3 +401,32 @@ def test_seed_fields_and_absmax_cache_of_the_gemm_wrappers():
     assert gemm.known_absmax(torch.ones(3, 2)) is None
     tensors[0].add_(1.0)                                  # a new version: neither entry applies
     assert gemm.known_absmax(tensors[0]) is None and gemm.absmax_cached(tensors[0]).item() == 2.0
+
+
+def test_needs_build_watches_the_internal_header(monkeypatch):
+    """The library is stale as soon as ANY file it is compiled from is newer than it: the sources, the public
+    header and every header beside the sources (found by listing the directory) — gcn_internal.h among them.
+    Driven through faked modification times: no file of the tree is touched."""
+    from pygcn_amd import build
+    internal = os.path.join(build.HERE, "csrc", "gcn_internal.h")
+    deps = build.deps()
+    assert internal in deps and os.path.join(ROOT, "include", "gcn_spmm.h") in deps
+    assert set(build.SRCS) <= set(deps) and all(os.path.isfile(d) for d in deps)
+    real_getmtime, real_exists = os.path.getmtime, os.path.exists
+    mtimes = {d: 1000.0 for d in deps}
+
+    def getmtime(path):
+        return mtimes[path] if path in mtimes else real_getmtime(path)
+
+    monkeypatch.setattr(build.os.path, "getmtime", getmtime)
+    monkeypatch.setattr(build.os.path, "exists", lambda path: path == build.OUT or real_exists(path))
+    mtimes[build.OUT] = 2000.0                  # newer than every dependency
+    assert not build.needs_build()
+    mtimes[internal] = 3000.0                   # the header alone is newer than the library
+    assert build.needs_build()
+    mtimes[internal] = 1000.0
+    for d in deps:                              # ... and so is every other dependency, one at a time
+        mtimes[d] = 3000.0
+        assert build.needs_build(), d
+        mtimes[d] = 1000.0
+    assert not build.needs_build()
