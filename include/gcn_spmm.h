@@ -948,6 +948,38 @@ int gcn_bn_linear_backward_sums(const float *ds, const float *z, const float *we
 int gcn_bn_linear_backward_apply(const float *ds, const float *z, const float *weight, const double *coef, float *dz,
                                  int64_t n_rows, int64_t Fin, int64_t Fout, int64_t batch, int relu, void *stream);
 
+/*
+ * Symmetric adjacencies (pygcn_amd/csrc/gcn_symmetric.hip).  All pointers DEVICE; nothing is read by the host.
+ *   gcn_sym_normalize_device  val <- D^-1/2 · val · D^-1/2 in place for a SQUARE CSR matrix (Kipf & Welling's
+ *                      normalisation; gcn_row_normalize_device is the reference's D^-1 form): entry e = (i, j)
+ *                      becomes (float)((double)val[e] / sqrt(d_i * d_j)), d = the row sums in DOUBLE, summed in a
+ *                      fixed order (lane-strided partials of one wavefront per row, then a shuffle tree), so two runs
+ *                      give the same bytes.  The product d_i * d_j is formed first and commutes, so (i, j) and (j, i)
+ *                      evaluate the same expression on the same operands: a matrix with bitwise symmetric weights
+ *                      comes out bitwise symmetric.  d_i * d_j == 0 gives 0 (`d_inv_sqrt[isinf] = 0`); a NaN in a row
+ *                      makes the entries of that row and of that column NaN and nothing else; a negative product
+ *                      gives NaN, as numpy's power does.  Two launches: the degrees into the workspace (double
+ *                      [n_rows], gcn_sym_normalize_workspace_bytes), then the scaling.  rowptr int32 or int64.
+ *   gcn_csr_mirror_device     for every stored entry e = (i, j) of a square CSR matrix, mirror[e] = the storage
+ *                      position of (j, i) — the lower bound of i among the columns of row j, if that position holds
+ *                      i — or -1.  counts: DEVICE int64 [4], zeroed here and filled by the kernels:
+ *                        [0] entries with no mirror;  [1] entries with mirror[mirror[e]] != e (duplicates);
+ *                        [2] entries whose column is not above that of the entry before them in their row;
+ *                        [3] entries whose value differs bitwise from their mirror's.
+ *                      [0] = [1] = [2] = 0 says: sorted, unique, pattern-symmetric — CSR(A^T) then has A's rowptr and
+ *                      col, and val_t[e] = val[mirror[e]].  One thread per entry (its row by binary search in rowptr),
+ *                      so a row of any length costs no more than its entries; every probe stays inside
+ *                      [rowptr[j], rowptr[j + 1]).  int32 rowptr only (nnz < 2^31): mirror holds 32-bit positions.
+ *   gcn_gather_f32     out[e] = src[index[e]] for e < n; an index outside [0, src_len) gives 0.
+ * (ABI 26, additive.)
+ */
+size_t gcn_sym_normalize_workspace_bytes(int64_t n_rows);
+int gcn_sym_normalize_device(const void *rowptr, int rowptr_is64, const int32_t *col, float *val, int64_t n_rows,
+                             void *workspace, size_t workspace_bytes, void *stream);
+int gcn_csr_mirror_device(const int32_t *rowptr, const int32_t *col, const float *val, int64_t n_rows, int64_t nnz,
+                          int32_t *mirror, int64_t *counts, void *stream);
+int gcn_gather_f32(const float *src, const int32_t *index, int64_t n, int64_t src_len, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,10 @@ SIGNATURES = {
     "gcn_bn_linear_forward": (i, [p, p, p, p, p, i64, i64, i64, i64, i, p]),
     "gcn_bn_linear_backward_sums": (i, [p, p, p, p, p, i64, i64, i64, i64, i, f32, p, p, p, sz, p]),
     "gcn_bn_linear_backward_apply": (i, [p, p, p, p, p, i64, i64, i64, i64, i, p]),
+    "gcn_sym_normalize_workspace_bytes": (sz, [i64]),
+    "gcn_sym_normalize_device": (i, [p, i, p, p, i64, p, sz, p]),
+    "gcn_csr_mirror_device": (i, [p, p, p, i64, i64, p, p, p]),
+    "gcn_gather_f32": (i, [p, p, i64, i64, p, p]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -96,6 +96,9 @@ class CSRGraph:
         self._plans_extra = {}        # chunk length -> (plan, arrays): plan(dtype) for bf16 storage
         self._t = None
         self._t_val_version = None
+        self._share_wanted = False    # share_transpose() was asked for: t() verifies and shares instead of sorting
+        self._share = None            # "self" / "pattern" while self._t is a shared transpose, else None
+        self._plan_owner = None       # the graph whose schedule arrays this one uses (a "pattern" transpose)
         self._inf_norm = None
         _BY_ARRAYS[_arrays_key(self.rowptr, self.col, self.val, self.shape)] = self
 
@@ -145,15 +148,20 @@ class CSRGraph:
 
     @classmethod
     def from_edge_list(cls, edges, n, device="cuda", symmetrize=True, self_loops=True,
-                       normalize=True, **kw):
+                       normalize=True, share_transpose=False, **kw):
         """The reference's adjacency recipe (pygcn/utils.py:360-368, kept there as a comment) on
         the device, from an [E, 2] array of (source, target) vertex ids:
             adj = coo_matrix(ones, (src, dst))                  duplicates SUMMED        :360-362
             adj = adj + adj.T*(adj.T > adj) - adj*(adj.T > adj)  = max(adj, adj.T)       :365
             adj = normalize(adj + I)                            D^-1 (A + I)            :368
         Every step is the native COO->CSR reduction (sum / max) or the native row normalisation.
+        `normalize`: True or "row" = D^-1 (A + I) as above; "sym" = D^-½ (A + I) D^-½, the normalisation of
+        Kipf & Welling's paper (sym_normalize_); False = none.  `share_transpose` calls share_transpose() on the
+        result: with `symmetrize` the pattern is symmetric, so the transpose needs no sort.
         Symmetrizing doubles the triplet count of the intermediate conversion: with `symmetrize` the
         input may hold fewer than 2³¹ pairs (from_coo's 2³² − 1 limit), checked before any launch."""
+        if isinstance(normalize, str) and normalize not in ("row", "sym"):
+            raise RuntimeError(f'from_edge_list: normalize must be True, False, "row" or "sym", got {normalize!r}')
         dev = torch.device(device)
         e = torch.as_tensor(edges).to(device=dev, dtype=torch.int64)
         if symmetrize and 2 * e.shape[0] + (n if self_loops else 0) >= 2 ** 32 - 1:
@@ -169,7 +177,13 @@ class CSRGraph:
             d = torch.arange(n, device=dev, dtype=torch.int64)
             g = cls.from_coo(torch.cat([r, d]), torch.cat([c, d]),
                              torch.cat([v, torch.ones(n, device=dev)]), (n, n), **kw)
-        return g.row_normalize_() if normalize else g
+        if normalize == "sym":         # (True == "sym" is False: True keeps meaning "row")
+            g.sym_normalize_()
+        elif normalize:
+            g.row_normalize_()
+        if share_transpose:
+            g.share_transpose()
+        return g
 
     def coo(self):
         """(row int64, col int64, val) of the stored entries, in CSR order."""
@@ -217,17 +231,26 @@ class CSRGraph:
             return self._plan_for(tuning.LONG_THRESH_BF16)
         if self._plan is not None:
             return self._plan
-        if self._keep is None:
-            self._keep = self._plan_arrays_device(self.long_thresh)
-        self._plan = self._plan_struct(self._keep, self.long_thresh if self.long_thresh > 0
+        self._plan = self._plan_struct(self._default_keep(), self.long_thresh if self.long_thresh > 0
                                        else _native.GCN_DEFAULT_LONG_THRESH)
         return self._plan
+
+    def _default_keep(self):
+        """The arrays of the default schedule: this graph's own, or those of the graph it shares its pattern with."""
+        if self._keep is None:
+            self._keep = (self._plan_owner._default_keep() if self._plan_owner is not None
+                          else self._plan_arrays_device(self.long_thresh))
+        return self._keep
 
     def _plan_for(self, thresh):
         """The schedule at another chunk length (cached beside the default one)."""
         hit = self._plans_extra.get(thresh)
         if hit is None:
-            keep = self._plan_arrays_device(thresh)
+            if self._plan_owner is not None:      # (same arrays; the struct differs in its val pointer)
+                self._plan_owner._plan_for(thresh)
+                keep = self._plan_owner._plans_extra[thresh][1]
+            else:
+                keep = self._plan_arrays_device(thresh)
             hit = self._plans_extra[thresh] = (self._plan_struct(keep, thresh), keep)
         return hit[0]
 
@@ -284,9 +307,12 @@ class CSRGraph:
     def t(self):
         """CSR(A^T), built once on the device by the native ingest kernel
         (`gcn_csr_transpose_device`: stable radix sort by column).  Within each row of A^T the
-        entries are in increasing source-row order, so backward sums are deterministic."""
+        entries are in increasing source-row order, so backward sums are deterministic.  After
+        share_transpose() a symmetric matrix needs no sort: the same arrays come from the mirror search."""
         if self._t is not None and self._t_val_version != self.val._version:
-            self._t = None        # the values were edited in place since the transpose was built
+            self._t = self._share = None   # the values were edited in place since the transpose was built
+        if self._t is None and self._share_wanted:
+            self._share_verified()         # (sets self._t unless the answer is "sort")
         if self._t is None:
             n_rows, n_cols = self.shape
             dev = self.device
@@ -304,6 +330,72 @@ class CSRGraph:
             g._t, g._t_val_version = self, val_t._version
             self._t, self._t_val_version = g, self.val._version
         return self._t
+
+    def share_transpose(self):
+        """Use the symmetry of this matrix for its transpose, if it has one: returns
+            "self"     sorted, unique, and every entry equal bit for bit to its mirror: t() is this graph;
+            "pattern"  sorted, unique, symmetric in its pattern only (the reference's recipe, row-normalised): t()
+                       is a CSRGraph that SHARES this graph's rowptr, col and schedule arrays and owns only its
+                       values, val_t[e] = val[mirror[e]] — the arrays `gcn_csr_transpose_device` would write, since
+                       a row of Âᵀ lists its entries in increasing source-row order, Â's sorted column order;
+            "sort"     anything else (also: not square, or a 64-bit row pointer): t() keeps the radix sort.
+        One mirror search on the device (`gcn_csr_mirror_device`) and ONE host read, of its four counters; the
+        mirror positions are dropped after the gather.  An in-place edit of `val` drops the shared transpose like
+        any cached one, and the next t() verifies again before it shares."""
+        self._share_wanted = True
+        self._t = self._share = None
+        return self._share_verified()
+
+    def _mirror_counts(self):
+        """(mirror int32 [nnz], counts int64 [4] on the device) of `gcn_csr_mirror_device`."""
+        mirror = torch.empty(max(self.nnz, 1), dtype=torch.int32, device=self.device)
+        counts = torch.empty(4, dtype=torch.int64, device=self.device)
+        _native.launch("gcn_csr_mirror_device", self.device, self.rowptr.data_ptr(), self.col.data_ptr(),
+                       self.val.data_ptr(), self.shape[0], self.nnz, mirror.data_ptr(), counts.data_ptr())
+        return mirror, counts
+
+    def _share_verified(self):
+        if self.shape[0] != self.shape[1] or self.rowptr.dtype != torch.int32:
+            self._share_wanted = False
+            return "sort"
+        mirror, counts = self._mirror_counts()
+        no_mirror, twice, unsorted, differ = counts.tolist()         # the one host read
+        if no_mirror or twice or unsorted:
+            self._share_wanted = False     # (a property of the pattern: no edit of the values changes it)
+            return "sort"
+        if not differ:
+            self._adopt_transpose(self, "self")
+            return "self"
+        val_t = torch.empty(self.nnz, dtype=torch.float32, device=self.device)
+        _native.launch("gcn_gather_f32", self.device, self.val.data_ptr(), mirror.data_ptr(), self.nnz, self.nnz,
+                       val_t.data_ptr())
+        self._adopt_transpose(self._pattern_twin(val_t), "pattern")
+        return "pattern"
+
+    def _pattern_twin(self, val_t):
+        """A CSRGraph on this graph's rowptr, col and schedule arrays with values of its own."""
+        g = CSRGraph(self.rowptr, self.col, val_t, (self.shape[1], self.shape[0]), item_cost=self.item_cost,
+                     long_thresh=self.long_thresh, validate=False)
+        g._plan_owner = self
+        return g
+
+    def _adopt_transpose(self, g, word):
+        self._t, self._t_val_version, self._share = g, self.val._version, word
+        if g is not self:
+            g._t, g._t_val_version = self, g.val._version
+
+    def sym_normalize_(self):
+        """In place D^-½ · A · D^-½ on the device (`gcn_sym_normalize_device`), Kipf & Welling's normalisation:
+        entry (i, j) becomes w / sqrt(d_i · d_j) with the row sums d in double; a zero product gives 0, a NaN stays in
+        its row and column.  Bitwise symmetric weights stay bitwise symmetric.  Square matrices only.  Invalidates
+        the cached transpose."""
+        if self.shape[0] != self.shape[1]:
+            raise RuntimeError(f"sym_normalize_: the matrix must be square, got {self.shape}")
+        _native.launch("gcn_sym_normalize_device", self.device, self.rowptr.data_ptr(),
+                       int(self.rowptr.dtype == torch.int64), self.col.data_ptr(), self.val.data_ptr(), self.shape[0],
+                       workspace=_native.lib().gcn_sym_normalize_workspace_bytes(self.shape[0]))
+        self._t = self._share = None
+        return self
 
     def take_rows(self, rows, col_map=None, n_cols=None):
         """The rows `rows` of this matrix as a CSRGraph of their own, with its own schedule: row r of the
@@ -357,7 +449,7 @@ class CSRGraph:
         transpose."""
         _native.launch("gcn_row_normalize_device", self.device, self.rowptr.data_ptr(),
                        int(self.rowptr.dtype == torch.int64), self.val.data_ptr(), self.shape[0])
-        self._t = None
+        self._t = self._share = None
         return self
 
     def inf_norm(self):
@@ -392,11 +484,19 @@ class CSRGraph:
             arrays[prefix + "long_row"] = k["long_row"][:k["n_long"]].cpu().numpy()
             arrays[prefix + "long_chunk0"] = k["long_chunk0"].cpu().numpy()
         put("a.", self)
+        share = None
         if with_transpose:
-            put("t.", self.t())
+            gt = self.t()
+            share = self._share           # a shared transpose is recorded as the relation, not as arrays:
+            if share == "pattern":        # "self" writes no t.* array, "pattern" only the values
+                arrays["t.val"] = gt.val.cpu().numpy()
+            elif share is None:
+                put("t.", gt)
         meta = {"n_rows": self.shape[0], "n_cols": self.shape[1], "nnz": self.nnz,
                 "item_cost": self.item_cost, "long_thresh": self.long_thresh,
-                "has_transpose": bool(with_transpose), "abi_version": _native.GCN_ABI_VERSION}
+                "has_transpose": bool(with_transpose) and share is None, "abi_version": _native.GCN_ABI_VERSION}
+        if share is not None:             # (optional key: files without it load as before)
+            meta["share_transpose"] = share
         return cache.write_file(path, meta, arrays)
 
     @classmethod
@@ -476,6 +576,21 @@ class CSRGraph:
             gt = get("t.", (meta["n_cols"], meta["n_rows"]))
             g._t, g._t_val_version = gt, g.val._version
             gt._t, gt._t_val_version = g, gt.val._version
+        share = meta.get("share_transpose")
+        if share is not None:
+            if share not in ("self", "pattern") or (share == "pattern" and (
+                    "t.val" not in arr or arr["t.val"].size != g.nnz or arr["t.val"].dtype != np.float32)):
+                raise cache.CacheFormatError(f"{path}: bad shared-transpose record")
+            g._share_wanted = True
+            if verify:      # the relation must be THE relation of the stored arrays: search again
+                word = g._share_verified()
+                if word != share or (share == "pattern" and not torch.equal(
+                        g._t.val.view(torch.int32), dev_t(arr["t.val"]).view(torch.int32))):
+                    raise cache.CacheFormatError(f"{path}: stored as a {share!r} transpose, the arrays say {word!r}")
+            elif share == "self":
+                g._adopt_transpose(g, "self")
+            else:
+                g._adopt_transpose(g._pattern_twin(dev_t(arr["t.val"])), "pattern")
         return g
 
     # ------------------------------------------------------------------ misc

@@ -31,13 +31,19 @@ VALUE_FLAGS = (
     ("--path", str, DEFAULT_CORA, "Directory with <dataset>.cites[/.content], a .cites file, or "
                                   "the committed edge-list fixture."),
     ("--dataset", str, "cora", "Dataset name inside --path."),
+    ("--normalization", str, "row", "Adjacency normalisation: row = D^-1 (A + I), the reference's; sym = "
+                                    "D^-1/2 (A + I) D^-1/2, Kipf & Welling's (extension)."),
 )
+CHOICES = {"--normalization": ("row", "sym")}
 SWITCHES = (
     ("--no-cuda", "Disables CUDA training (unsupported here: the path is HIP-only)."),
     ("--fastmode", "Validate during training pass."),
     ("--restrict_forward", "Run the forward pass on the receptive field of the rows it is asked for only "
                            "(extension, pygcn_amd/fused.py): training on idx_train, validation and test as "
                            "restricted passes of their own."),
+    ("--share_transpose", "Use the adjacency's symmetry for its transpose instead of sorting (extension, "
+                          "CSRGraph.share_transpose): the graph itself under --normalization sym, shared row "
+                          "pointers and columns under row."),
 )
 
 
@@ -46,7 +52,7 @@ def build_parser():
     for flag, help_text in SWITCHES:
         ap.add_argument(flag, action="store_true", default=False, help=help_text)
     for flag, kind, default, help_text in VALUE_FLAGS:
-        ap.add_argument(flag, type=kind, default=default, help=help_text)
+        ap.add_argument(flag, type=kind, default=default, help=help_text, choices=CHOICES.get(flag))
     return ap
 
 
@@ -59,7 +65,7 @@ class Run:
     def __init__(self, args):
         for seed_fn in (np.random.seed, torch.manual_seed, torch.cuda.manual_seed):
             seed_fn(args.seed)
-        data = load_data(args.path, args.dataset)
+        data = load_data(args.path, args.dataset, normalization=args.normalization)
         self.adj, self.features, self.labels = (t.cuda() for t in data[:3])
         self.split = dict(zip(("train", "val", "test"), (t.cuda() for t in data[3:])))
         self.model = GCN(nfeat=self.features.shape[1], nhid=args.hidden,
@@ -68,9 +74,11 @@ class Run:
                                     weight_decay=args.weight_decay)
         self.fastmode = args.fastmode
         self.restrict_forward = args.restrict_forward
-        if self.restrict_forward:      # (the restricted pass takes the prepared handle, not the COO tensor)
+        if self.restrict_forward or args.share_transpose:    # (both take the prepared handle, not the COO tensor)
             from pygcn_amd.graph import as_graph
             self.adj = as_graph(self.adj)
+        if args.share_transpose:
+            self.adj.share_transpose()
 
     def score(self, log_probs, name):
         rows = self.split[name]

@@ -35,6 +35,18 @@ def normalize(mx):
     return r_mat_inv.dot(mx)
 
 
+def normalize_sym(mx):
+    """Symmetrically normalize sparse matrix: D^-1/2 · mx · D^-1/2 with D the row sums, rows that sum to 0 stay 0
+    — the normalisation of Kipf & Welling's paper, which upstream's README names `normalize` a deviation from.
+    The host twin of CSRGraph.sym_normalize_, as `normalize` is of row_normalize_."""
+    rowsum = np.array(mx.sum(1), dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d_inv_sqrt = np.power(rowsum, -0.5).flatten()
+    d_inv_sqrt[np.isinf(d_inv_sqrt)] = 0.
+    d_mat = sp.diags(d_inv_sqrt)
+    return d_mat.dot(mx).dot(d_mat)
+
+
 def accuracy(output, labels):
     preds = output.max(1)[1].type_as(labels)
     correct = preds.eq(labels).double()
@@ -77,11 +89,14 @@ def synthetic_node_data(n, nfeat=1433, nclass=7, p=0.0127, seed=42):
     return features, labels
 
 
-def load_data(path=DEFAULT_CORA, dataset="cora"):
+def load_data(path=DEFAULT_CORA, dataset="cora", normalization="row"):
     """Upstream `load_data` (recipe at utils.py:356-383): citation graph -> symmetric adjacency
     -> normalize(A + I) -> torch sparse COO; features row-normalized; fixed index splits.
     `path` is a directory holding `<dataset>.cites` (and optionally `.content`), a `.cites` file,
-    or the committed edge-list fixture.  Without `.content`, features/labels are synthetic."""
+    or the committed edge-list fixture.  Without `.content`, features/labels are synthetic.
+    `normalization="sym"` normalizes the adjacency with normalize_sym instead (the features stay row-normalized)."""
+    if normalization not in ("row", "sym"):
+        raise ValueError(f'normalization must be "row" or "sym", got {normalization!r}')
     print('Loading {} dataset...'.format(dataset))
     edges, n, ifl = _cora_edges(path, dataset)
     if ifl is not None:
@@ -93,7 +108,7 @@ def load_data(path=DEFAULT_CORA, dataset="cora"):
     adj = sp.coo_matrix((np.ones(edges.shape[0]), (edges[:, 0], edges[:, 1])), shape=(n, n),
                         dtype=np.float32)
     adj = adj + adj.T.multiply(adj.T > adj) - adj.multiply(adj.T > adj)   # symmetrize
-    adj = normalize(adj + sp.eye(adj.shape[0]))
+    adj = (normalize if normalization == "row" else normalize_sym)(adj + sp.eye(adj.shape[0]))
     idx_train, idx_val, idx_test = range(140), range(200, 500), range(500, 1500)
     return (sparse_mx_to_torch_sparse_tensor(adj), torch.from_numpy(features),
             torch.from_numpy(np.asarray(labels, dtype=np.int64)), torch.LongTensor(idx_train),
