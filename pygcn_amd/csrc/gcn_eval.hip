@@ -58,8 +58,6 @@ namespace {
 
 constexpr int TV = 64;                   // vertices per tile: one wave = one sample's mask segment
 constexpr int kTileFloats = 8192;        // the LDS image, 32 KiB
-constexpr int64_t kBlocks = 2048;        // slabs of rows = partial rows
-constexpr int64_t kMaxBatch = 65535;     // sample groups ride on gridDim.y
 constexpr int64_t kMaxF = 64;
 
 struct Shape {
@@ -73,8 +71,9 @@ struct Shape {
         groups = (int)((batch + fit - 1) / fit);
         BS = (int)((batch + groups - 1) / groups);
         groups = (int)((batch + BS - 1) / BS);
-        blocks = std::min<int64_t>((n_rows + TV - 1) / TV, kBlocks);
-        rows_per_block = (int)((n_rows + TV * blocks - 1) / (TV * blocks)) * TV;
+        const TileSlabs sl(n_rows, TV);
+        blocks = sl.slabs;
+        rows_per_block = sl.rows_per_block;
     }
 };
 
@@ -297,7 +296,7 @@ __global__ __launch_bounds__(256) void eval_ingest_bwd_kernel(const float *__res
 
 bool shape_ok(int64_t n_rows, int64_t F, int64_t d, int64_t batch)
 {
-    return n_rows >= 1 && n_rows <= (int64_t)INT32_MAX * kBlocks && F >= 2 && F <= kMaxF && d >= 0 && d <= F - 1 &&
+    return n_rows >= 1 && n_rows <= (int64_t)INT32_MAX * kSlabBlocks && F >= 2 && F <= kMaxF && d >= 0 && d <= F - 1 &&
            batch >= 1 && batch <= kMaxBatch;
 }
 

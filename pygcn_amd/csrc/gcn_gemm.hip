@@ -2298,6 +2298,36 @@ using XwLogSoftmax = XwList<Xw<2, 7>>;
 
 }   // namespace
 
+// The caller's gcn_gemm_epilogue as the kernels' H2Epi, with the checks every X·W entry point makes; 0 = go on.
+// `bit_masks`: the entry point takes mask_bits / keep_bits_out (the 256-wide fp32 kernels); the others ignore them.
+static int epilogue_of(const char *who, const gcn_gemm_epilogue *epi, bool bit_masks, H2Epi &ep)
+{
+    ep = {};
+    if (epi == nullptr) return 0;
+    const uint32_t *mask_bits = bit_masks ? epi->mask_bits : nullptr;
+    const bool masked = epi->mask_src != nullptr || mask_bits != nullptr;
+    if (!(epi->dropout_p >= 0.f) || epi->dropout_p >= 1.f) return bad(who, GCN_E_BADARG, "dropout_p must be in [0, 1)");
+    if (epi->dropout_p > 0.f && !epi->relu)
+        return bad(who, GCN_E_BADARG, "dropout needs relu (out > 0 encodes the mask)");
+    if (masked && (epi->bias != nullptr || epi->relu || epi->dropout_p > 0.f))
+        return bad(who, GCN_E_BADARG, "forward epilogue and backward mask exclude each other");
+    ep.bias = epi->bias;
+    ep.relu = epi->relu ? 1 : 0;
+    ep.drop_thresh = gcn_dropout_threshold16(epi->dropout_p);
+    ep.drop_scale = gcn_dropout_scale16(ep.drop_thresh);
+    ep.drop_row_base = epi->drop_row_base;
+    ep.seed_lo = (uint32_t)epi->seed;
+    ep.seed_hi = (uint32_t)(epi->seed >> 32);
+    ep.seed_dev = epi->seed_dev;
+    ep.mask_src = epi->mask_src;          // (bf16 data at gcn_gemm_xw_bf16; typed per kernel)
+    ep.ld_mask = epi->ld_mask;
+    ep.mask_rows = masked ? epi->mask_rows : nullptr;
+    ep.mask_scale = epi->mask_scale;
+    ep.keep_bits_out = bit_masks ? epi->keep_bits_out : nullptr;
+    ep.mask_bits = mask_bits;
+    return 0;
+}
+
 // both decompositions of the 256 x 256 product (sch 0: two scaled fp16 parts, 1: three bf16 parts); every
 // error names `who`, the entry point that was called
 static int xw256_launch(const char *who, int sch, const float *X, int64_t ldx, const int32_t *x_rows, const float *W,
@@ -2310,31 +2340,10 @@ static int xw256_launch(const char *who, int sch, const float *X, int64_t ldx, c
         std::snprintf(msg, sizeof(msg), "%s%s", who, what);
         return msg;
     };
-    const float *mask_src = epi ? epi->mask_src : nullptr;
-    const int64_t ld_mask = epi ? epi->ld_mask : 0;
-    H2Epi ep = {};
-    if (epi != nullptr) {
-        if (!(epi->dropout_p >= 0.f) || epi->dropout_p >= 1.f)
-            return gcn_internal_fail(GCN_E_BADARG, named(": dropout_p must be in [0, 1)"));
-        if (epi->dropout_p > 0.f && !epi->relu)
-            return gcn_internal_fail(GCN_E_BADARG, named(": dropout needs relu (out > 0 encodes the mask)"));
-        if ((mask_src != nullptr || epi->mask_bits != nullptr) && (epi->bias != nullptr || epi->relu || epi->dropout_p > 0.f))
-            return gcn_internal_fail(GCN_E_BADARG, named(": forward epilogue and backward mask exclude each other"));
-        ep.bias = epi->bias;
-        ep.relu = epi->relu ? 1 : 0;
-        ep.drop_thresh = gcn_dropout_threshold16(epi->dropout_p);
-        ep.drop_scale = gcn_dropout_scale16(ep.drop_thresh);
-        ep.drop_row_base = epi->drop_row_base;
-        ep.seed_lo = (uint32_t)epi->seed;
-        ep.seed_hi = (uint32_t)(epi->seed >> 32);
-        ep.seed_dev = epi->seed_dev;
-        ep.mask_src = mask_src;
-        ep.ld_mask = ld_mask;
-        ep.mask_rows = (mask_src != nullptr || epi->mask_bits != nullptr) ? epi->mask_rows : nullptr;
-        ep.mask_scale = epi->mask_scale;
-        ep.keep_bits_out = epi->keep_bits_out;
-        ep.mask_bits = epi->mask_bits;
-    }
+    H2Epi ep;
+    if (int rc = epilogue_of(who, epi, true, ep)) return rc;
+    const float *mask_src = ep.mask_src;
+    const int64_t ld_mask = ep.ld_mask;
     if (M < 0 || ldx < kK || ldy < kN || ldw < kN)
         return gcn_internal_fail(GCN_E_BADARG, named(": bad sizes"));
     if (M == 0) return 0;
@@ -2434,33 +2443,12 @@ int gcn_gemm_xw_bf16(const void *X, int64_t ldx, const void *W, int64_t ldw, voi
                      int64_t M, int64_t K, int64_t N, const gcn_gemm_epilogue *epi, void *workspace,
                      size_t workspace_bytes, void *stream)
 {
-    H2Epi ep = {};
-    if (epi != nullptr) {
-        if (!(epi->dropout_p >= 0.f) || epi->dropout_p >= 1.f)
-            return gcn_internal_fail(GCN_E_BADARG, "gcn_gemm_xw_bf16: dropout_p must be in [0, 1)");
-        if (epi->dropout_p > 0.f && !epi->relu)
-            return gcn_internal_fail(GCN_E_BADARG, "gcn_gemm_xw_bf16: dropout needs relu (out > 0 encodes the mask)");
-        if (epi->mask_src != nullptr) {
-            if (epi->bias != nullptr || epi->relu || epi->dropout_p > 0.f)
-                return gcn_internal_fail(GCN_E_BADARG, "gcn_gemm_xw_bf16: forward epilogue and backward mask exclude each other");
-            if (((uintptr_t)epi->mask_src) % 16 != 0 || epi->ld_mask % 8 != 0 || epi->ld_mask < N)
-                return gcn_internal_fail(GCN_E_ALIGN, "gcn_gemm_xw_bf16: mask rows must be 16-byte aligned bf16 [*, N]");
-            ep.mask_src = (const float *)epi->mask_src;      // (bf16 data; typed per kernel)
-            ep.ld_mask = epi->ld_mask;
-            ep.mask_rows = epi->mask_rows;
-            ep.mask_scale = epi->mask_scale;
-        }
-        if (((uintptr_t)epi->bias) % 16 != 0)
-            return gcn_internal_fail(GCN_E_ALIGN, "gcn_gemm_xw_bf16: bias must be 16-byte aligned");
-        ep.bias = epi->bias;
-        ep.relu = epi->relu ? 1 : 0;
-        ep.drop_thresh = gcn_dropout_threshold16(epi->dropout_p);
-        ep.drop_scale = gcn_dropout_scale16(ep.drop_thresh);
-        ep.drop_row_base = epi->drop_row_base;
-        ep.seed_lo = (uint32_t)epi->seed;
-        ep.seed_hi = (uint32_t)(epi->seed >> 32);
-        ep.seed_dev = epi->seed_dev;
-    }
+    H2Epi ep;
+    if (int rc = epilogue_of("gcn_gemm_xw_bf16", epi, false, ep)) return rc;
+    if (ep.mask_src != nullptr && (((uintptr_t)ep.mask_src) % 16 != 0 || ep.ld_mask % 8 != 0 || ep.ld_mask < N))
+        return gcn_internal_fail(GCN_E_ALIGN, "gcn_gemm_xw_bf16: mask rows must be 16-byte aligned bf16 [*, N]");
+    if (((uintptr_t)ep.bias) % 16 != 0)
+        return gcn_internal_fail(GCN_E_ALIGN, "gcn_gemm_xw_bf16: bias must be 16-byte aligned");
     const bool fwd = ep.bias != nullptr || ep.relu || ep.drop_thresh != 0u;
     const size_t need = gcn_gemm_bf16_workspace_bytes(K, N);
     if (need == 0)

@@ -56,7 +56,6 @@
 namespace {
 
 constexpr int TV = 64;                   // vertices per tile: one wave, a lane per vertex
-constexpr int64_t kBlocks = 2048;        // slabs of rows = partial rows
 constexpr int64_t kMaxC = 64, kMaxT = 32, kMaxH = 64, kMinRows = 64;
 constexpr int kStat = 64;                // pitch of the statistics and coefficient vectors
 constexpr size_t kLdsDefault = 64 * 1024;          // what a launch may ask for without opting in
@@ -715,8 +714,9 @@ struct Shape {
         rowD = row_doubles(HP);
         rowF = row_floats(K, HP);
         // the workspace holds B = min(tiles, 2048) partial rows; the launch uses the blocks that have rows
-        const int64_t B = std::min<int64_t>((n_rows + TV - 1) / TV, kBlocks);
-        rows_per_block = (int)((n_rows + TV * B - 1) / (TV * B)) * TV;
+        const TileSlabs sl(n_rows, TV);
+        const int64_t B = sl.slabs;
+        rows_per_block = sl.rows_per_block;
         blocks = (n_rows + rows_per_block - 1) / rows_per_block;
         auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
         offF = up((size_t)B * rowD * sizeof(double));

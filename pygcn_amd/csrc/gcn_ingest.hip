@@ -246,22 +246,20 @@ int gcn_csr_transpose_device(const void *rowptr, int rowptr_is64, const int32_t 
     const unsigned blocks = (unsigned)std::min<int64_t>((std::max<int64_t>(nnz, n_cols + 1) + 255) / 256,
                                                         256 * 32);
     if (nnz > 0) {
-        if (rowptr_is64)
-            hipLaunchKernelGGL(pack_entries_kernel<int64_t>, dim3(blocks), dim3(256), 0, s,
-                               (const int64_t *)rowptr, val, n_rows, nnz, pay_in);
-        else
-            hipLaunchKernelGGL(pack_entries_kernel<int32_t>, dim3(blocks), dim3(256), 0, s,
-                               (const int32_t *)rowptr, val, n_rows, nnz, pay_in);
+        pick_index(rowptr_is64 != 0, [&](auto i) {
+            typedef typename decltype(i)::type I;
+            hipLaunchKernelGGL(pack_entries_kernel<I>, dim3(blocks), dim3(256), 0, s, (const I *)rowptr, val, n_rows,
+                               nnz, pay_in);
+        });
         hipError_t e = hipcub::DeviceRadixSort::SortPairs((void *)w, temp, col, keys_sorted, pay_in,
                                                           pay_out, nnz, 0, bits, s);
         if (e != hipSuccess) return ifail_hip(e, "gcn_csr_transpose_device: radix sort");
     }
-    if (rowptr_is64)
-        hipLaunchKernelGGL(unpack_entries_kernel<int64_t>, dim3(blocks), dim3(256), 0, s, pay_out,
-                           keys_sorted, n_cols, nnz, (int64_t *)rowptr_t, col_t, val_t);
-    else
-        hipLaunchKernelGGL(unpack_entries_kernel<int32_t>, dim3(blocks), dim3(256), 0, s, pay_out,
-                           keys_sorted, n_cols, nnz, (int32_t *)rowptr_t, col_t, val_t);
+    pick_index(rowptr_is64 != 0, [&](auto i) {
+        typedef typename decltype(i)::type I;
+        hipLaunchKernelGGL(unpack_entries_kernel<I>, dim3(blocks), dim3(256), 0, s, pay_out, keys_sorted, n_cols, nnz,
+                           (I *)rowptr_t, col_t, val_t);
+    });
     return launched("gcn_csr_transpose_device: launch");
 }
 
@@ -319,14 +317,11 @@ int gcn_coo_to_csr_device(const int64_t *row, const int64_t *col, const float *v
     hipLaunchKernelGGL(coo_heads_kernel, dim3(blocks), dim3(256), 0, s, key_sorted, nnz, outpos);
     e = hipcub::DeviceScan::ExclusiveSum((void *)w, temp, outpos, outpos, nnz + 1, s);
     if (e != hipSuccess) return ifail_hip(e, "gcn_coo_to_csr_device: scan");
-    if (rowptr_is64)
-        hipLaunchKernelGGL(coo_reduce_kernel<int64_t>, dim3(blocks), dim3(256), 0, s, key_sorted,
-                           pos_sorted, outpos, val, nnz, n_rows, n_cols, reduce == GCN_REDUCE_MAX,
-                           (int64_t *)rowptr_out, col_out, val_out, nnz_out);
-    else
-        hipLaunchKernelGGL(coo_reduce_kernel<int32_t>, dim3(blocks), dim3(256), 0, s, key_sorted,
-                           pos_sorted, outpos, val, nnz, n_rows, n_cols, reduce == GCN_REDUCE_MAX,
-                           (int32_t *)rowptr_out, col_out, val_out, nnz_out);
+    pick_index(rowptr_is64 != 0, [&](auto i) {
+        typedef typename decltype(i)::type I;
+        hipLaunchKernelGGL(coo_reduce_kernel<I>, dim3(blocks), dim3(256), 0, s, key_sorted, pos_sorted, outpos, val,
+                           nnz, n_rows, n_cols, reduce == GCN_REDUCE_MAX, (I *)rowptr_out, col_out, val_out, nnz_out);
+    });
     return launched("gcn_coo_to_csr_device: launch");
 }
 
@@ -339,12 +334,10 @@ int gcn_row_normalize_device(const void *rowptr, int rowptr_is64, float *val, in
     if (val == nullptr) return ifail(GCN_E_BADARG, "gcn_row_normalize_device: val is NULL");
     const unsigned blocks = (unsigned)std::min<int64_t>((n_rows + 3) / 4, 256 * 64);
     hipStream_t s = (hipStream_t)stream;
-    if (rowptr_is64)
-        hipLaunchKernelGGL(row_normalize_kernel<int64_t>, dim3(blocks), dim3(256), 0, s,
-                           (const int64_t *)rowptr, val, n_rows);
-    else
-        hipLaunchKernelGGL(row_normalize_kernel<int32_t>, dim3(blocks), dim3(256), 0, s,
-                           (const int32_t *)rowptr, val, n_rows);
+    pick_index(rowptr_is64 != 0, [&](auto i) {
+        typedef typename decltype(i)::type I;
+        hipLaunchKernelGGL(row_normalize_kernel<I>, dim3(blocks), dim3(256), 0, s, (const I *)rowptr, val, n_rows);
+    });
     return launched("gcn_row_normalize_device: launch");
 }
 

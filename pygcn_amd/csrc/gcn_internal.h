@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 
 #include "gcn_spmm.h"
 
@@ -39,6 +40,8 @@ static inline float gcn_dropout_scale16(uint32_t thresh)
 
 namespace {
 
+typedef uint16_t bf16_t;                 // raw bf16 bits
+
 // "<who>: <what>" as the library's last error; returns code
 [[maybe_unused]] int bad(const char *who, int code, const char *what)
 {
@@ -60,10 +63,74 @@ namespace {
     return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, who);
 }
 
+// ------------------------------------------------------------------------------------------------
+// shape rules that more than one file's sweeps share
+// ------------------------------------------------------------------------------------------------
+constexpr int64_t kMaxBatch = 65535;     // windows / sample groups ride on gridDim.y
+constexpr int64_t kSlabBlocks = 2048;    // slabs of rows = partial rows of a full-height sweep
+
+// elements per 16-byte lane (Lane<T>::V on the device side)
+[[maybe_unused]] int64_t lane_elems(int dtype) { return dtype == GCN_DTYPE_BF16 ? 8 : 4; }
+
+// a row of F elements as 16-byte lanes, F / width of them dividing a 256-thread block
+[[maybe_unused]] bool lane_width_ok(int64_t F, int dtype)
+{
+    if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16) return false;
+    const int64_t v = lane_elems(dtype);
+    return F >= v && F <= 256 * v && (F % v) == 0 && (256 % (F / v)) == 0;
+}
+
+// n_rows >= 1 rows as at most kSlabBlocks contiguous slabs, of 64 rows at least, one per block
+struct RowSlabs {
+    int64_t blocks;
+    int rows_per_block;
+    explicit RowSlabs(int64_t n_rows)
+    {
+        blocks = std::min<int64_t>((n_rows + 63) / 64, kSlabBlocks);
+        rows_per_block = (int)((n_rows + blocks - 1) / blocks);
+    }
+};
+
+// the same in whole tiles of `tile` rows: `slabs` = min(tiles, kSlabBlocks) is what a workspace is sized by
+struct TileSlabs {
+    int64_t slabs;
+    int rows_per_block;
+    TileSlabs(int64_t n_rows, int64_t tile)
+    {
+        slabs = std::min<int64_t>((n_rows + tile - 1) / tile, kSlabBlocks);
+        rows_per_block = (int)((n_rows + tile * slabs - 1) / (tile * slabs)) * (int)tile;
+    }
+};
+
+// ------------------------------------------------------------------------------------------------
+// THE PICKS: how an entry point turns a run-time argument into a template argument.  The callable gets the choice
+// as a value whose TYPE carries it (a generic lambda reads it back with `typename decltype(t)::type` or
+// `decltype(v)::value`), so a launch is written once and only the instantiations some branch names exist.
+// A kernel's template-id with a comma in it goes in parentheses inside hipLaunchKernelGGL.
+// ------------------------------------------------------------------------------------------------
+template <typename T> struct TypeTag { typedef T type; };
+
+// f(TypeTag<float>) for GCN_DTYPE_F32, f(TypeTag<bf16_t>) otherwise (the caller has checked dtype)
+template <typename F> auto pick_dtype(int dtype, F &&f)
+{
+    if (dtype == GCN_DTYPE_F32) return f(TypeTag<float>{});
+    return f(TypeTag<bf16_t>{});
+}
+// f(TypeTag<int64_t>) or f(TypeTag<int32_t>): the width of a CSR row pointer
+template <typename F> auto pick_index(bool is64, F &&f)
+{
+    if (is64) return f(TypeTag<int64_t>{});
+    return f(TypeTag<int32_t>{});
+}
+// f(std::integral_constant<int, V>) for the V of the list that equals v; false, and no call, when none does
+template <int... Vs, typename F> bool pick_int(int v, F &&f)
+{
+    return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+
 // ================================================================================================
 // device side
 // ================================================================================================
-typedef uint16_t bf16_t;                 // raw bf16 bits
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -109,6 +176,45 @@ template <> struct Lane<bf16_t> {
         Raw r = {pack_bf16x2(x[0], x[1]), pack_bf16x2(x[2], x[3]), pack_bf16x2(x[4], x[5]),
                  pack_bf16x2(x[6], x[7])};
         return r;
+    }
+};
+
+// four consecutive elements of a row <-> four floats (8-byte aligned at bf16, 16-byte at fp32).  Two stores:
+// store_rounded rounds fp32 to bf16 (nearest even); store_exact takes the upper halves, for values that ARE
+// bf16 numbers already.  At fp32 the two are the same store.
+template <typename T> struct Run4;
+template <> struct Run4<float> {
+    static __device__ __forceinline__ void load(const float *p, float (&x)[4])
+    {
+        const float4 v = *(const float4 *)p;
+        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+    }
+    static __device__ __forceinline__ void store_rounded(float *p, const float (&x)[4])
+    {
+        *(float4 *)p = make_float4(x[0], x[1], x[2], x[3]);
+    }
+    static __device__ __forceinline__ void store_exact(float *p, const float (&x)[4]) { store_rounded(p, x); }
+};
+template <> struct Run4<bf16_t> {
+    static __device__ __forceinline__ void load(const bf16_t *p, float (&x)[4])
+    {
+        const uint2 v = *(const uint2 *)p;
+        x[0] = __uint_as_float(v.x << 16); x[1] = __uint_as_float(v.x & 0xffff0000u);
+        x[2] = __uint_as_float(v.y << 16); x[3] = __uint_as_float(v.y & 0xffff0000u);
+    }
+    static __device__ __forceinline__ void store_rounded(bf16_t *p, const float (&x)[4])
+    {
+        uint2 v;
+        v.x = pack_bf16x2(x[0], x[1]);
+        v.y = pack_bf16x2(x[2], x[3]);
+        *(uint2 *)p = v;
+    }
+    static __device__ __forceinline__ void store_exact(bf16_t *p, const float (&x)[4])
+    {
+        uint2 v;
+        v.x = (__float_as_uint(x[0]) >> 16) | (__float_as_uint(x[1]) & 0xffff0000u);
+        v.y = (__float_as_uint(x[2]) >> 16) | (__float_as_uint(x[3]) & 0xffff0000u);
+        *(uint2 *)p = v;
     }
 };
 

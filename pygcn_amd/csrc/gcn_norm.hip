@@ -299,6 +299,7 @@ __global__ __launch_bounds__(1024) void bn_finish_kernel(const double *__restric
             out1[o] = (float)v;
             out2[o] = (float)(1.0 / sqrt(v + (double)eps));
         } else {
+            // (nl_finish of gcn_normlin.hip repeats these lines: the two must agree to the bit)
             const double d = a[2] / n;                   // mean - mean32
             double v = a[3] / n - d * d;
             v = v < 0.0 ? 0.0 : v;
@@ -525,54 +526,26 @@ __global__ __launch_bounds__(256) void attn_backward_kernel(const T *__restrict_
     block_combine<V>(s, red, p, partial + p.slot() * C);
 }
 
-constexpr int64_t kBlocks = 2048;        // slabs of rows = partial rows (bwd_colsum_kernel's grid)
-constexpr int64_t kMaxBatch = 65535;     // windows ride on gridDim.y
+bool rows_ok(int64_t n_rows, int64_t min_rows) { return n_rows >= min_rows && n_rows <= (int64_t)INT32_MAX * kSlabBlocks; }
 
-struct Slabs {
-    int64_t blocks;
-    int rows_per_block;
-    explicit Slabs(int64_t n_rows)
-    {
-        blocks = std::min<int64_t>((n_rows + 63) / 64, kBlocks);
-        rows_per_block = (int)((n_rows + blocks - 1) / blocks);
-    }
-};
-
-bool width_ok(int64_t F, int dtype)
-{
-    if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16) return false;
-    const int64_t v = dtype == GCN_DTYPE_BF16 ? 8 : 4;   // elements per 16-byte lane
-    return F >= v && F <= 256 * v && (F % v) == 0 && (256 % (F / v)) == 0;
-}
-
-bool shape_ok(int64_t n_rows, int64_t F, int dtype)
-{
-    return n_rows >= 2 && n_rows <= (int64_t)INT32_MAX * kBlocks && width_ok(F, dtype);
-}
+bool shape_ok(int64_t n_rows, int64_t F, int dtype) { return rows_ok(n_rows, 2) && lane_width_ok(F, dtype); }
 
 bool batch_ok(int64_t batch) { return batch >= 1 && batch <= kMaxBatch; }
 
-// the argument checks every BatchNorm entry point shares; 0 = go on
-int check(const char *who, int dtype, int64_t n_rows, int64_t F, int64_t batch, bool null_ptr, uintptr_t tensors)
-{
-    if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16) return bad(who, GCN_E_BADARG, "unknown dtype");
-    if (!shape_ok(n_rows, F, dtype))
-        return bad(who, GCN_E_BADARG,
-                   "needs n_rows >= 2 and F a multiple of the 16-byte lane width with F/width dividing 256");
-    if (!batch_ok(batch)) return bad(who, GCN_E_BADARG, "needs 1 <= batch <= 65535");
-    if (null_ptr) return bad(who, GCN_E_BADARG, "NULL pointer");
-    if (tensors % 16 != 0) return bad(who, GCN_E_ALIGN, "16-byte alignment required");
-    return 0;
-}
+// how few rows a sweep takes, and the sentence that says so: BatchNorm needs two, the pool and attention sweeps one
+struct RowsRule {
+    int64_t min_rows;
+    const char *text;
+};
+constexpr RowsRule kBnRows = {2, "needs n_rows >= 2 and F a multiple of the 16-byte lane width with F/width dividing 256"};
+constexpr RowsRule kPoolRows = {1, "needs n_rows >= 1 and C a multiple of the 16-byte lane width with C/width dividing 256"};
 
-// the same for the two pool sweeps, which take a single row
-int check_pool(const char *who, int dtype, int64_t n_rows, int64_t C, int64_t batch, bool null_ptr,
-               uintptr_t tensors)
+// the argument checks every entry point of this file with a [n_rows, batch * F] tensor shares; 0 = go on
+int check(const char *who, const RowsRule &rule, int dtype, int64_t n_rows, int64_t F, int64_t batch, bool null_ptr,
+          uintptr_t tensors)
 {
     if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16) return bad(who, GCN_E_BADARG, "unknown dtype");
-    if (n_rows < 1 || n_rows > (int64_t)INT32_MAX * kBlocks || !width_ok(C, dtype))
-        return bad(who, GCN_E_BADARG,
-                   "needs n_rows >= 1 and C a multiple of the 16-byte lane width with C/width dividing 256");
+    if (!rows_ok(n_rows, rule.min_rows) || !lane_width_ok(F, dtype)) return bad(who, GCN_E_BADARG, rule.text);
     if (!batch_ok(batch)) return bad(who, GCN_E_BADARG, "needs 1 <= batch <= 65535");
     if (null_ptr) return bad(who, GCN_E_BADARG, "NULL pointer");
     if (tensors % 16 != 0) return bad(who, GCN_E_ALIGN, "16-byte alignment required");
@@ -585,22 +558,21 @@ dim3 finish_grid(int64_t F, int64_t batch) { return dim3((unsigned)((F + 31) / 3
 int stats(const char *who, int dtype, const void *z, int64_t n_rows, int64_t F, int64_t batch, int relu, float eps,
           float *mean, float *var, float *rstd, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (int rc = check(who, dtype, n_rows, F, batch,
+    if (int rc = check(who, kBnRows, dtype, n_rows, F, batch,
                        z == nullptr || mean == nullptr || var == nullptr || rstd == nullptr, (uintptr_t)z))
         return rc;
     if (workspace == nullptr || workspace_bytes < gcn_bn_batched_workspace_bytes(n_rows, F, batch, dtype))
         return bad(who, GCN_E_WORKSPACE, "workspace too small");
     if ((uintptr_t)workspace % 16 != 0) return bad(who, GCN_E_ALIGN, "16-byte alignment required");
-    const Slabs sl(n_rows);
+    const RowSlabs sl(n_rows);
     const dim3 grid((unsigned)sl.blocks, (unsigned)batch), block(256);
     hipStream_t s = (hipStream_t)stream;
     double *part = (double *)workspace;
-    if (dtype == GCN_DTYPE_F32)
-        hipLaunchKernelGGL(bn_stats_kernel<float>, grid, block, 0, s, (const float *)z, part, n_rows, (int)F, relu,
+    pick_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(bn_stats_kernel<T>, grid, block, 0, s, (const T *)z, part, n_rows, (int)F, relu,
                            sl.rows_per_block);
-    else
-        hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)z, part, n_rows, (int)F, relu,
-                           sl.rows_per_block);
+    });
     hipLaunchKernelGGL(bn_finish_kernel<2>, finish_grid(F, batch), dim3(1024), 0, s, (const double *)part,
                        (int)sl.blocks, (int)F, (double)n_rows, eps, (const float *)nullptr, mean, var, rstd,
                        (double *)nullptr);
@@ -610,19 +582,18 @@ int stats(const char *who, int dtype, const void *z, int64_t n_rows, int64_t F, 
 int apply(const char *who, int dtype, const void *z, void *y, int64_t n_rows, int64_t F, int64_t batch, int relu,
           const float *mean, const float *rstd, const float *gamma, const float *beta, void *stream)
 {
-    if (int rc = check(who, dtype, n_rows, F, batch,
+    if (int rc = check(who, kBnRows, dtype, n_rows, F, batch,
                        z == nullptr || y == nullptr || mean == nullptr || rstd == nullptr,
                        (uintptr_t)z | (uintptr_t)y))
         return rc;
-    const Slabs sl(n_rows);
+    const RowSlabs sl(n_rows);
     const dim3 grid((unsigned)sl.blocks, (unsigned)batch), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == GCN_DTYPE_F32)
-        hipLaunchKernelGGL(bn_apply_kernel<float>, grid, block, 0, s, (const float *)z, (float *)y, n_rows, (int)F,
-                           relu, sl.rows_per_block, mean, rstd, gamma, beta);
-    else
-        hipLaunchKernelGGL(bn_apply_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)z, (bf16_t *)y, n_rows,
-                           (int)F, relu, sl.rows_per_block, mean, rstd, gamma, beta);
+    pick_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(bn_apply_kernel<T>, grid, block, 0, s, (const T *)z, (T *)y, n_rows, (int)F, relu,
+                           sl.rows_per_block, mean, rstd, gamma, beta);
+    });
     return launched(who);
 }
 
@@ -630,7 +601,7 @@ int backward_sums(const char *who, int dtype, const void *g, const void *z, int6
                   int64_t batch, int relu, float eps, const float *mean, float *sum_g, float *sum_gxhat,
                   double *coef, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (int rc = check(who, dtype, n_rows, F, batch,
+    if (int rc = check(who, kBnRows, dtype, n_rows, F, batch,
                        g == nullptr || z == nullptr || mean == nullptr || sum_g == nullptr ||
                            sum_gxhat == nullptr || coef == nullptr,
                        (uintptr_t)g | (uintptr_t)z))
@@ -639,16 +610,15 @@ int backward_sums(const char *who, int dtype, const void *g, const void *z, int6
         return bad(who, GCN_E_WORKSPACE, "workspace too small");
     if ((uintptr_t)workspace % 16 != 0 || (uintptr_t)coef % 8 != 0)
         return bad(who, GCN_E_ALIGN, "16-byte alignment required (coef: 8)");
-    const Slabs sl(n_rows);
+    const RowSlabs sl(n_rows);
     const dim3 grid((unsigned)sl.blocks, (unsigned)batch), block(256);
     hipStream_t s = (hipStream_t)stream;
     double *part = (double *)workspace;
-    if (dtype == GCN_DTYPE_F32)
-        hipLaunchKernelGGL(bn_bwd_sums_kernel<float>, grid, block, 0, s, (const float *)g, (const float *)z, part,
-                           n_rows, (int)F, relu, sl.rows_per_block, mean);
-    else
-        hipLaunchKernelGGL(bn_bwd_sums_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)g, (const bf16_t *)z, part,
-                           n_rows, (int)F, relu, sl.rows_per_block, mean);
+    pick_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(bn_bwd_sums_kernel<T>, grid, block, 0, s, (const T *)g, (const T *)z, part, n_rows, (int)F,
+                           relu, sl.rows_per_block, mean);
+    });
     hipLaunchKernelGGL(bn_finish_kernel<4>, finish_grid(F, batch), dim3(1024), 0, s, (const double *)part,
                        (int)sl.blocks, (int)F, (double)n_rows, eps, mean, sum_g, sum_gxhat, (float *)nullptr, coef);
     return launched(who);
@@ -657,20 +627,19 @@ int backward_sums(const char *who, int dtype, const void *g, const void *z, int6
 int backward_apply(const char *who, int dtype, const void *g, const void *z, void *dz, int64_t n_rows, int64_t F,
                    int64_t batch, int relu, const float *gamma, const double *coef, void *stream)
 {
-    if (int rc = check(who, dtype, n_rows, F, batch,
+    if (int rc = check(who, kBnRows, dtype, n_rows, F, batch,
                        g == nullptr || z == nullptr || dz == nullptr || coef == nullptr,
                        (uintptr_t)g | (uintptr_t)z | (uintptr_t)dz))
         return rc;
     if ((uintptr_t)coef % 8 != 0) return bad(who, GCN_E_ALIGN, "coef: 8-byte alignment required");
-    const Slabs sl(n_rows);
+    const RowSlabs sl(n_rows);
     const dim3 grid((unsigned)sl.blocks, (unsigned)batch), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == GCN_DTYPE_F32)
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, grid, block, 0, s, (const float *)g, (const float *)z,
-                           (float *)dz, n_rows, (int)F, relu, sl.rows_per_block, gamma, coef);
-    else
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)g, (const bf16_t *)z,
-                           (bf16_t *)dz, n_rows, (int)F, relu, sl.rows_per_block, gamma, coef);
+    pick_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, grid, block, 0, s, (const T *)g, (const T *)z, (T *)dz, n_rows,
+                           (int)F, relu, sl.rows_per_block, gamma, coef);
+    });
     return launched(who);
 }
 
@@ -681,7 +650,7 @@ extern "C" {
 size_t gcn_bn_workspace_bytes(int64_t n_rows, int64_t F, int dtype)
 {
     if (!shape_ok(n_rows, F, dtype)) return 0;
-    return (size_t)Slabs(n_rows).blocks * 4 * (size_t)F * sizeof(double);    // backward: 4 sums per block
+    return (size_t)RowSlabs(n_rows).blocks * 4 * (size_t)F * sizeof(double);    // backward: 4 sums per block
 }
 
 size_t gcn_bn_batched_workspace_bytes(int64_t n_rows, int64_t F, int64_t batch, int dtype)
@@ -747,31 +716,30 @@ int gcn_bn_backward_apply_batched(int dtype, const void *g, const void *z, void 
 
 size_t gcn_pool_workspace_bytes(int64_t n_rows, int64_t C, int64_t batch, int dtype)
 {
-    if (n_rows < 1 || n_rows > (int64_t)INT32_MAX * kBlocks || !width_ok(C, dtype) || !batch_ok(batch)) return 0;
-    return (size_t)batch * (size_t)Slabs(n_rows).blocks * (size_t)C * sizeof(double);   // one sum per block
+    if (!rows_ok(n_rows, 1) || !lane_width_ok(C, dtype) || !batch_ok(batch)) return 0;
+    return (size_t)batch * (size_t)RowSlabs(n_rows).blocks * (size_t)C * sizeof(double);   // one sum per block
 }
 
 int gcn_masked_colsum(int dtype, const void *h, const float *mask, int64_t n_rows, int64_t C, int64_t batch,
                       double *sums, void *workspace, size_t workspace_bytes, void *stream)
 {
     const char *who = "gcn_masked_colsum";
-    if (int rc = check_pool(who, dtype, n_rows, C, batch, h == nullptr || mask == nullptr || sums == nullptr,
+    if (int rc = check(who, kPoolRows, dtype, n_rows, C, batch, h == nullptr || mask == nullptr || sums == nullptr,
                             (uintptr_t)h))
         return rc;
     if (workspace == nullptr || workspace_bytes < gcn_pool_workspace_bytes(n_rows, C, batch, dtype))
         return bad(who, GCN_E_WORKSPACE, "workspace too small");
     if ((uintptr_t)workspace % 16 != 0 || (uintptr_t)sums % 8 != 0 || (uintptr_t)mask % 4 != 0)
         return bad(who, GCN_E_ALIGN, "16-byte alignment required (sums: 8, mask: 4)");
-    const Slabs sl(n_rows);
+    const RowSlabs sl(n_rows);
     const dim3 grid((unsigned)sl.blocks, (unsigned)batch), block(256);
     hipStream_t s = (hipStream_t)stream;
     double *part = (double *)workspace;
-    if (dtype == GCN_DTYPE_F32)
-        hipLaunchKernelGGL(pool_colsum_kernel<float>, grid, block, 0, s, (const float *)h, mask, part, n_rows,
-                           (int)C, sl.rows_per_block);
-    else
-        hipLaunchKernelGGL(pool_colsum_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)h, mask, part, n_rows,
-                           (int)C, sl.rows_per_block);
+    pick_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(pool_colsum_kernel<T>, grid, block, 0, s, (const T *)h, mask, part, n_rows, (int)C,
+                           sl.rows_per_block);
+    });
     hipLaunchKernelGGL(bn_finish_kernel<1>, finish_grid(C, batch), dim3(1024), 0, s, (const double *)part,
                        (int)sl.blocks, (int)C, 1.0, 0.f, (const float *)nullptr, (float *)nullptr, (float *)nullptr,
                        (float *)nullptr, sums);
@@ -782,35 +750,34 @@ int gcn_masked_broadcast(int dtype, const float *mask, const float *coef, void *
                          int64_t batch, void *stream)
 {
     const char *who = "gcn_masked_broadcast";
-    if (int rc = check_pool(who, dtype, n_rows, C, batch, mask == nullptr || coef == nullptr || dh == nullptr,
+    if (int rc = check(who, kPoolRows, dtype, n_rows, C, batch, mask == nullptr || coef == nullptr || dh == nullptr,
                             (uintptr_t)dh))
         return rc;
     if ((uintptr_t)mask % 4 != 0 || (uintptr_t)coef % 4 != 0)
         return bad(who, GCN_E_ALIGN, "mask, coef: 4-byte alignment required");
-    const Slabs sl(n_rows);
+    const RowSlabs sl(n_rows);
     const dim3 grid((unsigned)sl.blocks, (unsigned)batch), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == GCN_DTYPE_F32)
-        hipLaunchKernelGGL(pool_broadcast_kernel<float>, grid, block, 0, s, mask, coef, (float *)dh, n_rows, (int)C,
+    pick_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(pool_broadcast_kernel<T>, grid, block, 0, s, mask, coef, (T *)dh, n_rows, (int)C,
                            sl.rows_per_block);
-    else
-        hipLaunchKernelGGL(pool_broadcast_kernel<bf16_t>, grid, block, 0, s, mask, coef, (bf16_t *)dh, n_rows,
-                           (int)C, sl.rows_per_block);
+    });
     return launched(who);
 }
 
 size_t gcn_attn_workspace_bytes(int64_t n_rows, int64_t C, int64_t batch, int dtype)
 {
-    if (n_rows < 1 || n_rows > (int64_t)INT32_MAX * kBlocks || !width_ok(C, dtype) || !batch_ok(batch)) return 0;
+    if (!rows_ok(n_rows, 1) || !lane_width_ok(C, dtype) || !batch_ok(batch)) return 0;
     // scores: one (max, sum) pair per block; backward: one partial row [C] per block
-    return (size_t)batch * (size_t)Slabs(n_rows).blocks * (size_t)std::max<int64_t>(C, 2) * sizeof(double);
+    return (size_t)batch * (size_t)RowSlabs(n_rows).blocks * (size_t)std::max<int64_t>(C, 2) * sizeof(double);
 }
 
 int gcn_attn_scores(int dtype, const void *h, const float *key, int64_t n_rows, int64_t C, int64_t batch,
                     float *scores, double *stats, void *workspace, size_t workspace_bytes, void *stream)
 {
     const char *who = "gcn_attn_scores";
-    if (int rc = check_pool(who, dtype, n_rows, C, batch,
+    if (int rc = check(who, kPoolRows, dtype, n_rows, C, batch,
                             h == nullptr || key == nullptr || scores == nullptr || stats == nullptr, (uintptr_t)h))
         return rc;
     if (workspace == nullptr || workspace_bytes < gcn_attn_workspace_bytes(n_rows, C, batch, dtype))
@@ -818,16 +785,15 @@ int gcn_attn_scores(int dtype, const void *h, const float *key, int64_t n_rows, 
     if ((uintptr_t)workspace % 16 != 0 || (uintptr_t)stats % 8 != 0 || (uintptr_t)key % 4 != 0 ||
         (uintptr_t)scores % 4 != 0)
         return bad(who, GCN_E_ALIGN, "16-byte alignment required (stats: 8, key, scores: 4)");
-    const Slabs sl(n_rows);
+    const RowSlabs sl(n_rows);
     const dim3 grid((unsigned)sl.blocks, (unsigned)batch), block(256);
     hipStream_t s = (hipStream_t)stream;
     double *part = (double *)workspace;
-    if (dtype == GCN_DTYPE_F32)
-        hipLaunchKernelGGL(attn_scores_kernel<float>, grid, block, 0, s, (const float *)h, key, scores, part, n_rows,
-                           (int)C, sl.rows_per_block);
-    else
-        hipLaunchKernelGGL(attn_scores_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)h, key, scores, part,
-                           n_rows, (int)C, sl.rows_per_block);
+    pick_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(attn_scores_kernel<T>, grid, block, 0, s, (const T *)h, key, scores, part, n_rows, (int)C,
+                           sl.rows_per_block);
+    });
     hipLaunchKernelGGL(attn_finish_kernel, dim3((unsigned)batch), block, 0, s, (const double *)part, (int)sl.blocks,
                        stats);
     return launched(who);
@@ -837,7 +803,7 @@ int gcn_attn_normalize(const float *scores, const double *stats, float *attn, in
                        void *stream)
 {
     const char *who = "gcn_attn_normalize";
-    if (n_rows < 1 || n_rows > (int64_t)INT32_MAX * kBlocks) return bad(who, GCN_E_BADARG, "needs n_rows >= 1");
+    if (!rows_ok(n_rows, 1)) return bad(who, GCN_E_BADARG, "needs n_rows >= 1");
     if (!batch_ok(batch)) return bad(who, GCN_E_BADARG, "needs 1 <= batch <= 65535");
     if (scores == nullptr || stats == nullptr || attn == nullptr) return bad(who, GCN_E_BADARG, "NULL pointer");
     if ((uintptr_t)stats % 8 != 0 || (uintptr_t)scores % 4 != 0 || (uintptr_t)attn % 4 != 0)
@@ -852,7 +818,7 @@ int gcn_attn_backward(int dtype, const void *h, const float *ds, const float *ke
                       void *stream)
 {
     const char *who = "gcn_attn_backward";
-    if (int rc = check_pool(who, dtype, n_rows, C, batch,
+    if (int rc = check(who, kPoolRows, dtype, n_rows, C, batch,
                             h == nullptr || ds == nullptr || key == nullptr || dkey == nullptr,
                             (uintptr_t)h | (uintptr_t)dh))
         return rc;
@@ -861,16 +827,15 @@ int gcn_attn_backward(int dtype, const void *h, const float *ds, const float *ke
     if ((uintptr_t)workspace % 16 != 0 || (uintptr_t)dkey % 8 != 0 || (uintptr_t)key % 4 != 0 ||
         (uintptr_t)ds % 4 != 0)
         return bad(who, GCN_E_ALIGN, "16-byte alignment required (dkey: 8, key, ds: 4)");
-    const Slabs sl(n_rows);
+    const RowSlabs sl(n_rows);
     const dim3 grid((unsigned)sl.blocks, (unsigned)batch), block(256);
     hipStream_t s = (hipStream_t)stream;
     double *part = (double *)workspace;
-    if (dtype == GCN_DTYPE_F32)
-        hipLaunchKernelGGL(attn_backward_kernel<float>, grid, block, 0, s, (const float *)h, ds, key, (float *)dh,
-                           part, n_rows, (int)C, sl.rows_per_block);
-    else
-        hipLaunchKernelGGL(attn_backward_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)h, ds, key, (bf16_t *)dh,
-                           part, n_rows, (int)C, sl.rows_per_block);
+    pick_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(attn_backward_kernel<T>, grid, block, 0, s, (const T *)h, ds, key, (T *)dh, part, n_rows,
+                           (int)C, sl.rows_per_block);
+    });
     hipLaunchKernelGGL(bn_finish_kernel<1>, finish_grid(C, batch), dim3(1024), 0, s, (const double *)part,
                        (int)sl.blocks, (int)C, 1.0, 0.f, (const float *)nullptr, (float *)nullptr, (float *)nullptr,
                        (float *)nullptr, dkey);

@@ -70,7 +70,6 @@ constexpr int kWaves = 4;                 // per block
 constexpr int kThreads = 64 * kWaves;
 constexpr int64_t kMaxBlocks = 512;
 constexpr int kRow = kF * kF + 4 * kF;    // doubles per partial row: P[32][32], sum dy, sum dy t, sum t, sum t^2
-constexpr int64_t kMaxBatch = 65535;      // windows ride on gridDim.y
 
 // (x - mean) * rstd, rounded after the subtraction and after the product (bn_apply_kernel's expression)
 __device__ __forceinline__ float normalised(float x, float mu, float rs)

@@ -27,36 +27,6 @@ namespace {
 constexpr int kWave = 64;
 constexpr int kRowsPerBlock = 4;          // one wave per row, 4 waves per workgroup
 
-template <typename T> struct Quad;       // 4 consecutive elements of a row <-> 4 floats
-template <> struct Quad<float> {
-    typedef float4 Raw;
-    static __device__ __forceinline__ void load(const float *p, float (&x)[4])
-    {
-        const float4 v = *(const float4 *)p;
-        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-    }
-    static __device__ __forceinline__ void store(float *p, const float (&x)[4])
-    {
-        *(float4 *)p = make_float4(x[0], x[1], x[2], x[3]);
-    }
-};
-template <> struct Quad<bf16_t> {
-    static __device__ __forceinline__ void load(const bf16_t *p, float (&x)[4])
-    {
-        const uint2 v = *(const uint2 *)p;
-        x[0] = __uint_as_float(v.x << 16); x[1] = __uint_as_float(v.x & 0xffff0000u);
-        x[2] = __uint_as_float(v.y << 16); x[3] = __uint_as_float(v.y & 0xffff0000u);
-    }
-    static __device__ __forceinline__ void store(bf16_t *p, const float (&x)[4])
-    {
-        // (the values ARE bf16 numbers: truncation is exact)
-        uint2 v;
-        v.x = (__float_as_uint(x[0]) >> 16) | (__float_as_uint(x[1]) & 0xffff0000u);
-        v.y = (__float_as_uint(x[2]) >> 16) | (__float_as_uint(x[3]) & 0xffff0000u);
-        *(uint2 *)p = v;
-    }
-};
-
 __device__ __forceinline__ int below(unsigned long long m)      // set bits of m in lanes below this one
 {
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -87,7 +57,7 @@ __global__ __launch_bounds__(kWave *kRowsPerBlock) void pack_count_kernel(
         uint32_t nib = 0u;
         if (f < F) {
             float x[4];
-            Quad<T>::load(row + f, x);
+            Run4<T>::load(row + f, x);
 #pragma unroll
             for (int k = 0; k < 4; ++k) nib |= (x[k] != 0.f ? 1u : 0u) << k;
         }
@@ -113,7 +83,7 @@ __global__ __launch_bounds__(kWave *kRowsPerBlock) void pack_values_kernel(
     for (int f0 = 0; f0 < F; f0 += 4 * kWave) {
         const int f = f0 + 4 * lane;
         float x[4] = {0.f, 0.f, 0.f, 0.f};
-        if (f < F) Quad<T>::load(row + f, x);
+        if (f < F) Run4<T>::load(row + f, x);
         // position of element (lane, k) among the non-zeros of the slab, in row order (4·lane + k):
         // all non-zeros of lower lanes + the non-zeros of this lane at lower k
         unsigned long long b[4];
@@ -170,7 +140,7 @@ __global__ __launch_bounds__(kWave *kRowsPerBlock) void unpack_kernel(
                 ++pos;
             }
         }
-        if (f < F) Quad<T>::store(dst + r * ldd + f, x);
+        if (f < F) Run4<T>::store_exact(dst + r * ldd + f, x);      // (the values ARE bf16 numbers)
         base += total;
     }
 }
@@ -293,10 +263,10 @@ int gcn_rows_pack_count(int dtype, const void *src, int64_t ld, const int64_t *r
     if (((uintptr_t)src) % 16 != 0) return gcn_internal_fail(GCN_E_ALIGN, "gcn_rows_pack_count: 16-byte alignment required");
     const dim3 grid((unsigned)((m + kRowsPerBlock - 1) / kRowsPerBlock)), block(kWave * kRowsPerBlock);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == GCN_DTYPE_F32)
-        hipLaunchKernelGGL(pack_count_kernel<float>, grid, block, 0, s, (const float *)src, ld, rows, m, (int)F, bits, counts);
-    else
-        hipLaunchKernelGGL(pack_count_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)src, ld, rows, m, (int)F, bits, counts);
+    pick_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(pack_count_kernel<T>, grid, block, 0, s, (const T *)src, ld, rows, m, (int)F, bits, counts);
+    });
     return launched("gcn_rows_pack_count launch");
 }
 
@@ -311,10 +281,11 @@ int gcn_rows_pack_values(int dtype, const void *src, int64_t ld, const int64_t *
     if (((uintptr_t)src) % 16 != 0) return gcn_internal_fail(GCN_E_ALIGN, "gcn_rows_pack_values: 16-byte alignment required");
     const dim3 grid((unsigned)((m + kRowsPerBlock - 1) / kRowsPerBlock)), block(kWave * kRowsPerBlock);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == GCN_DTYPE_F32)
-        hipLaunchKernelGGL(pack_values_kernel<float>, grid, block, 0, s, (const float *)src, ld, rows, m, (int)F, offsets, (float *)vals);
-    else
-        hipLaunchKernelGGL(pack_values_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)src, ld, rows, m, (int)F, offsets, (bf16_t *)vals);
+    pick_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(pack_values_kernel<T>, grid, block, 0, s, (const T *)src, ld, rows, m, (int)F, offsets, (T
+                           *)vals);
+    });
     return launched("gcn_rows_pack_values launch");
 }
 
@@ -329,10 +300,11 @@ int gcn_rows_unpack(int dtype, const uint32_t *bits, const int64_t *offsets, con
     if (((uintptr_t)dst) % 16 != 0) return gcn_internal_fail(GCN_E_ALIGN, "gcn_rows_unpack: 16-byte alignment required");
     const dim3 grid((unsigned)((m + kRowsPerBlock - 1) / kRowsPerBlock)), block(kWave * kRowsPerBlock);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == GCN_DTYPE_F32)
-        hipLaunchKernelGGL(unpack_kernel<float>, grid, block, 0, s, bits, offsets, (const float *)vals, m, (int)F, (float *)dst, ldd);
-    else
-        hipLaunchKernelGGL(unpack_kernel<bf16_t>, grid, block, 0, s, bits, offsets, (const bf16_t *)vals, m, (int)F, (bf16_t *)dst, ldd);
+    pick_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(unpack_kernel<T>, grid, block, 0, s, bits, offsets, (const T *)vals, m, (int)F, (T *)dst,
+                           ldd);
+    });
     return launched("gcn_rows_unpack launch");
 }
 

@@ -238,24 +238,22 @@ int gcn_plan_count_device(const void *rowptr, int rowptr_is64, int64_t n_rows, i
     carve(workspace, n_rows, &ws);
     const int64_t m = n_rows + 1;
     const dim3 grid(grid_for(m)), block(256);
-    if (rowptr_is64)
-        hipLaunchKernelGGL(plan_rows_kernel<int64_t>, grid, block, 0, s, (const int64_t *)rowptr,
-                           n_rows, item_cost, long_thresh, ws);
-    else
-        hipLaunchKernelGGL(plan_rows_kernel<int32_t>, grid, block, 0, s, (const int32_t *)rowptr,
-                           n_rows, item_cost, long_thresh, ws);
+    pick_index(rowptr_is64 != 0, [&](auto i) {
+        typedef typename decltype(i)::type I;
+        hipLaunchKernelGGL(plan_rows_kernel<I>, grid, block, 0, s, (const I *)rowptr, n_rows, item_cost, long_thresh,
+                           ws);
+    });
     size_t tb = ws.scan_temp_bytes;
     hipError_t e = hipcub::DeviceScan::ExclusiveSum(ws.scan_temp, tb, ws.cost, ws.cost, m, s);
     if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(ws.scan_temp, tb, ws.chunks, ws.chunks, m, s);
     if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(ws.scan_temp, tb, ws.long_rank, ws.long_rank, m, s);
     if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(ws.scan_temp, tb, ws.short_rank, ws.short_rank, m, s);
     if (e != hipSuccess) return gcn_internal_fail_hip((int)e, "gcn_plan_count_device: scan");
-    if (rowptr_is64)
-        hipLaunchKernelGGL(plan_short_kernel<int64_t>, grid, block, 0, s, (const int64_t *)rowptr,
-                           n_rows, item_cost, long_thresh, ws);
-    else
-        hipLaunchKernelGGL(plan_short_kernel<int32_t>, grid, block, 0, s, (const int32_t *)rowptr,
-                           n_rows, item_cost, long_thresh, ws);
+    pick_index(rowptr_is64 != 0, [&](auto i) {
+        typedef typename decltype(i)::type I;
+        hipLaunchKernelGGL(plan_short_kernel<I>, grid, block, 0, s, (const I *)rowptr, n_rows, item_cost, long_thresh,
+                           ws);
+    });
     int rounds = 0;
     while (((int64_t)1 << rounds) < m) ++rounds;      // 2^rounds >= n_short + 1
     for (int k = 0; k < rounds; ++k)
@@ -284,14 +282,11 @@ int gcn_plan_fill_device(const void *rowptr, int rowptr_is64, int64_t n_rows, in
     PlanWs ws;
     carve(const_cast<void *>(workspace), n_rows, &ws);
     const dim3 grid(grid_for(n_rows + 1)), block(256);
-    if (rowptr_is64)
-        hipLaunchKernelGGL(plan_fill_kernel<int64_t>, grid, block, 0, s, (const int64_t *)rowptr, n_rows,
-                           long_thresh, ws, items, n_items, chunk_row, chunk_e0, n_chunks, long_row,
-                           long_chunk0, n_long);
-    else
-        hipLaunchKernelGGL(plan_fill_kernel<int32_t>, grid, block, 0, s, (const int32_t *)rowptr, n_rows,
-                           long_thresh, ws, items, n_items, chunk_row, chunk_e0, n_chunks, long_row,
-                           long_chunk0, n_long);
+    pick_index(rowptr_is64 != 0, [&](auto i) {
+        typedef typename decltype(i)::type I;
+        hipLaunchKernelGGL(plan_fill_kernel<I>, grid, block, 0, s, (const I *)rowptr, n_rows, long_thresh, ws, items,
+                           n_items, chunk_row, chunk_e0, n_chunks, long_row, long_chunk0, n_long);
+    });
     return launched("gcn_plan_fill_device: launch");
 }
 

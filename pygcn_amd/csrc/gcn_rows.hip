@@ -34,37 +34,11 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kBitRows = kBlock / 2;      // rows of one workgroup of the one-bit form
 
-template <typename T> struct Run4;       // four consecutive elements of a row <-> four floats
-template <> struct Run4<float> {
-    static __device__ __forceinline__ void load(const float *p, float (&x)[4])
-    {
-        const float4 v = *(const float4 *)p;
-        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-    }
-    static __device__ __forceinline__ void store(float *p, const float (&x)[4])
-    {
-        *(float4 *)p = make_float4(x[0], x[1], x[2], x[3]);
-    }
-    static __device__ __forceinline__ float get(const float *p) { return *p; }
-    static __device__ __forceinline__ void put(float *p, float x) { *p = x; }
-};
-template <> struct Run4<bf16_t> {
-    static __device__ __forceinline__ void load(const bf16_t *p, float (&x)[4])
-    {
-        const uint2 v = *(const uint2 *)p;
-        x[0] = __uint_as_float(v.x << 16); x[1] = __uint_as_float(v.x & 0xffff0000u);
-        x[2] = __uint_as_float(v.y << 16); x[3] = __uint_as_float(v.y & 0xffff0000u);
-    }
-    static __device__ __forceinline__ void store(bf16_t *p, const float (&x)[4])
-    {
-        uint2 v;
-        v.x = pack_bf16x2(x[0], x[1]);
-        v.y = pack_bf16x2(x[2], x[3]);
-        *(uint2 *)p = v;
-    }
-    static __device__ __forceinline__ float get(const bf16_t *p) { return __uint_as_float(((uint32_t)*p) << 16); }
-    static __device__ __forceinline__ void put(bf16_t *p, float x) { *p = (bf16_t)(pack_bf16x2(x, 0.f) & 0xffffu); }
-};
+// one element of a row <-> a float, where a run of four cannot travel as one access
+__device__ __forceinline__ float get(const float *p) { return *p; }
+__device__ __forceinline__ void put(float *p, float x) { *p = x; }
+__device__ __forceinline__ float get(const bf16_t *p) { return __uint_as_float(((uint32_t)*p) << 16); }
+__device__ __forceinline__ void put(bf16_t *p, float x) { *p = (bf16_t)(pack_bf16x2(x, 0.f) & 0xffffu); }
 
 // h[f .. f + 4) of one row (p points at column f; `left` = F - f > 0 columns remain) under four keep
 // flags: kept elements are multiplied by s in fp32 and rounded once, the others become +0
@@ -76,11 +50,11 @@ __device__ __forceinline__ void drop_run(T *p, int64_t left, bool vec, const boo
         Run4<T>::load(p, x);
 #pragma unroll
         for (int j = 0; j < 4; ++j) x[j] = keep[j] ? x[j] * s : 0.f;
-        Run4<T>::store(p, x);
+        Run4<T>::store_rounded(p, x);
     } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            if (j < left) Run4<T>::put(p + j, keep[j] ? Run4<T>::get(p + j) * s : 0.f);
+            if (j < left) put(p + j, keep[j] ? get(p + j) * s : 0.f);
     }
 }
 
@@ -226,7 +200,7 @@ int gcn_dropout_rows(int dtype, void *h, int64_t ld, const int64_t *rows, int64_
         return gcn_internal_fail(GCN_E_BADARG, "gcn_dropout_rows: need m >= 0, F >= 1 and ld >= F");
     if (m == 0 || dropout_p == 0.f) return 0;
     if (h == nullptr) return gcn_internal_fail(GCN_E_BADARG, "gcn_dropout_rows: NULL pointer");
-    const size_t esize = dtype == GCN_DTYPE_F32 ? 4 : 2;
+    const size_t esize = pick_dtype(dtype, [](auto t) { return sizeof(typename decltype(t)::type); });
     if (((uintptr_t)h) % esize != 0) return gcn_internal_fail(GCN_E_ALIGN, "gcn_dropout_rows: h is not element-aligned");
     DropParams p;
     p.rows = rows; p.m = m; p.F = F; p.ld = ld; p.row_base = drop_row_base;
@@ -240,20 +214,20 @@ int gcn_dropout_rows(int dtype, void *h, int64_t ld, const int64_t *rows, int64_
         if (slabs > INT_MAX || spans > 65535)
             return gcn_internal_fail(GCN_E_BADARG, "gcn_dropout_rows: m or F too large for one launch");
         const dim3 grid((unsigned)slabs, (unsigned)spans), block(kBlock);
-        if (dtype == GCN_DTYPE_F32)
-            hipLaunchKernelGGL(dropout_rows_bits_kernel<float>, grid, block, 0, s, (float *)h, p);
-        else
-            hipLaunchKernelGGL(dropout_rows_bits_kernel<bf16_t>, grid, block, 0, s, (bf16_t *)h, p);
+        pick_dtype(dtype, [&](auto t) {
+            typedef typename decltype(t)::type T;
+            hipLaunchKernelGGL(dropout_rows_bits_kernel<T>, grid, block, 0, s, (T *)h, p);
+        });
     } else {
         const int64_t G = 2 * ((F + 15) / 16);
         if (G > INT_MAX || m > INT64_MAX / G)
             return gcn_internal_fail(GCN_E_BADARG, "gcn_dropout_rows: m * F too large");
         const int64_t blocks = std::min<int64_t>((m * G + kBlock - 1) / kBlock, 1 << 20);   // (grid-stride beyond)
         const dim3 grid((unsigned)blocks), block(kBlock);
-        if (dtype == GCN_DTYPE_F32)
-            hipLaunchKernelGGL(dropout_rows_fields_kernel<float>, grid, block, 0, s, (float *)h, p);
-        else
-            hipLaunchKernelGGL(dropout_rows_fields_kernel<bf16_t>, grid, block, 0, s, (bf16_t *)h, p);
+        pick_dtype(dtype, [&](auto t) {
+            typedef typename decltype(t)::type T;
+            hipLaunchKernelGGL(dropout_rows_fields_kernel<T>, grid, block, 0, s, (T *)h, p);
+        });
     }
     return launched("gcn_dropout_rows launch");
 }
@@ -269,15 +243,13 @@ int gcn_csr_take_rows(const void *rowptr, int rowptr_is64, const int32_t *col, c
     // (col / val / col_out / val_out may be NULL when no selected row holds an entry: nothing is then touched)
     const dim3 grid(4096), block(kBlock);       // grid-stride: the entry count is rowptr_out[m], on the device
     hipStream_t s = (hipStream_t)stream;
-#define GCN_TAKE(PI, PO)                                                                                        \
-    hipLaunchKernelGGL((take_rows_kernel<PI, PO>), grid, block, 0, s, rowptr, col, val, rows, m, col_map, \
-                       rowptr_out, col_out, val_out, n_unmapped)
-    if (rowptr_is64) {
-        if (out_is64) GCN_TAKE(int64_t, int64_t); else GCN_TAKE(int64_t, int32_t);
-    } else {
-        if (out_is64) GCN_TAKE(int32_t, int64_t); else GCN_TAKE(int32_t, int32_t);
-    }
-#undef GCN_TAKE
+    pick_index(rowptr_is64 != 0, [&](auto pi) {
+        pick_index(out_is64 != 0, [&](auto po) {
+            hipLaunchKernelGGL((take_rows_kernel<typename decltype(pi)::type, typename decltype(po)::type>), grid,
+                               block,
+                               0, s, rowptr, col, val, rows, m, col_map, rowptr_out, col_out, val_out, n_unmapped);
+        });
+    });
     return launched("gcn_csr_take_rows launch");
 }
 

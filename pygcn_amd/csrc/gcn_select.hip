@@ -54,7 +54,6 @@ constexpr int kPasses = 3;
 constexpr int kState = 8;                 // uint32 per window: prefix, rank, count_gt (+ padding)
 constexpr int64_t kBlocks = 1024;         // slabs of rows per window
 constexpr int64_t kRowsPerBlock = 1024;   // a block's slab is at least this long before a second block starts
-constexpr int64_t kMaxBatch = 65535;      // windows ride on gridDim.y
 constexpr int64_t kMaxRows = INT32_MAX;   // n_rows < 2^31: counts and ranks are int32
 
 __device__ __forceinline__ uint32_t order_key(float f)

@@ -1290,71 +1290,45 @@ __global__ __launch_bounds__(1024) void colsum_finish_kernel(const float *__rest
 // ------------------------------------------------------------------------------------------
 // host-side dispatch
 // ------------------------------------------------------------------------------------------
-template <typename T, int VEC, int LPR>
-void launch_narrow(const KParams &kp, bool is64, dim3 grid, hipStream_t s)
+// XEPI, the extras of a store: 2 = row flags / maximum (log_softmax or not), 1 = log_softmax alone, 0 = none.
+// LPR = lpr for the powers of two below 64, and 64 for anything else.
+template <typename T, int VEC>
+void launch_narrow(const KParams &kp, bool is64, int lpr, dim3 grid, hipStream_t s)
 {
     const dim3 block(kWave * kWavesPerBlock);
-    const int xepi = (kp.cflag != nullptr || kp.cabsmax != nullptr) ? 2 : (kp.log_softmax ? 1 : 0);   // extras
-#define GCN_LAUNCH_NARROW(I, X) \
-    hipLaunchKernelGGL((spmm_narrow_kernel<T, VEC, LPR, I, X>), grid, block, 0, s, kp)
-    if (xepi == 2) {
-        if (is64) GCN_LAUNCH_NARROW(int64_t, 2);
-        else GCN_LAUNCH_NARROW(int32_t, 2);
-    } else if (xepi == 1) {
-        if (is64) GCN_LAUNCH_NARROW(int64_t, 1);
-        else GCN_LAUNCH_NARROW(int32_t, 1);
-    } else {
-        if (is64) GCN_LAUNCH_NARROW(int64_t, 0);
-        else GCN_LAUNCH_NARROW(int32_t, 0);
-    }
-#undef GCN_LAUNCH_NARROW
+    const int xepi = (kp.cflag != nullptr || kp.cabsmax != nullptr) ? 2 : (kp.log_softmax ? 1 : 0);
+    auto go = [&](auto l) {
+        pick_int<0, 1, 2>(xepi, [&](auto x) {
+            pick_index(is64, [&](auto i) {
+                hipLaunchKernelGGL((spmm_narrow_kernel<T, VEC, decltype(l)::value, typename decltype(i)::type,
+                                                       decltype(x)::value>),
+                                   grid, block, 0, s, kp);
+            });
+        });
+    };
+    if (!pick_int<1, 2, 4, 8, 16, 32>(lpr, go)) go(std::integral_constant<int, 64>{});
 }
 
-template <typename T, int VEC>
-void launch_narrow_lpr(const KParams &kp, bool is64, int lpr, dim3 grid, hipStream_t s)
-{
-    switch (lpr) {
-    case 1: launch_narrow<T, VEC, 1>(kp, is64, grid, s); break;
-    case 2: launch_narrow<T, VEC, 2>(kp, is64, grid, s); break;
-    case 4: launch_narrow<T, VEC, 4>(kp, is64, grid, s); break;
-    case 8: launch_narrow<T, VEC, 8>(kp, is64, grid, s); break;
-    case 16: launch_narrow<T, VEC, 16>(kp, is64, grid, s); break;
-    case 32: launch_narrow<T, VEC, 32>(kp, is64, grid, s); break;
-    default: launch_narrow<T, VEC, 64>(kp, is64, grid, s); break;
-    }
-}
-
+// FLAGS = operand hint / row selection.  It has no log_softmax-alone form (XEPI 1): there log_softmax takes the
+// full-extras instantiation.  Without FLAGS, XEPI 1 is the last layer of every forward pass: log_softmax without
+// the row-flag / maximum code.
 template <typename T, int VEC>
 void launch_wide(const KParams &kp, bool is64, dim3 grid, hipStream_t s)
 {
     constexpr int D = 8;
     const dim3 block(kWave * kWavesPerBlock);
-    const bool xepi = kp.log_softmax || kp.cflag != nullptr || kp.cabsmax != nullptr;
-#define GCN_LAUNCH_WIDE(I, FL, X) \
-    hipLaunchKernelGGL((spmm_wide_kernel<T, VEC, I, D, FL, X>), grid, block, 0, s, kp)
-    if (kp.bflag != nullptr || kp.csel != nullptr) {   // operand hint / row selection: the flag variant
-        if (xepi) {
-            if (is64) GCN_LAUNCH_WIDE(int64_t, true, 2);
-            else GCN_LAUNCH_WIDE(int32_t, true, 2);
-        } else {
-            if (is64) GCN_LAUNCH_WIDE(int64_t, true, 0);
-            else GCN_LAUNCH_WIDE(int32_t, true, 0);
-        }
-    } else {
-        if (kp.log_softmax && kp.cflag == nullptr && kp.cabsmax == nullptr) {
-            // the last layer of every forward pass: log_softmax only, without the row-flag / maximum
-            // code of the full-extras instantiation
-            if (is64) GCN_LAUNCH_WIDE(int64_t, false, 1);
-            else GCN_LAUNCH_WIDE(int32_t, false, 1);
-        } else if (xepi) {
-            if (is64) GCN_LAUNCH_WIDE(int64_t, false, 2);
-            else GCN_LAUNCH_WIDE(int32_t, false, 2);
-        } else {
-            if (is64) GCN_LAUNCH_WIDE(int64_t, false, 0);
-            else GCN_LAUNCH_WIDE(int32_t, false, 0);
-        }
-    }
-#undef GCN_LAUNCH_WIDE
+    const bool flags = kp.bflag != nullptr || kp.csel != nullptr;
+    const bool extras = kp.cflag != nullptr || kp.cabsmax != nullptr;
+    const int xepi = (extras || (flags && kp.log_softmax)) ? 2 : (kp.log_softmax ? 1 : 0);
+    auto go = [&](auto fl, auto x) {
+        pick_index(is64, [&](auto i) {
+            hipLaunchKernelGGL((spmm_wide_kernel<T, VEC, typename decltype(i)::type, D, decltype(fl)::value,
+                                                 decltype(x)::value>),
+                               grid, block, 0, s, kp);
+        });
+    };
+    if (flags) pick_int<0, 2>(xepi, [&](auto x) { go(std::true_type{}, x); });
+    else pick_int<0, 1, 2>(xepi, [&](auto x) { go(std::false_type{}, x); });
 }
 
 int next_pow2(int v)
@@ -1385,8 +1359,9 @@ int spmm_typed(const gcn_csr_plan *plan, KParams &kp, hipStream_t s)
         if (kp.packed != nullptr) {
             if constexpr (sizeof(T) == 4) {      // (fp32, F = 256, aligned: gcn_spmm_csr_packed checked)
                 const dim3 grid(nblk, 1), block(kWave * kWavesPerBlock);
-                if (is64) hipLaunchKernelGGL((spmm_wide_packed_kernel<int64_t, 8>), grid, block, 0, s, kp);
-                else hipLaunchKernelGGL((spmm_wide_packed_kernel<int32_t, 8>), grid, block, 0, s, kp);
+                pick_index(is64, [&](auto i) {
+                    hipLaunchKernelGGL((spmm_wide_packed_kernel<typename decltype(i)::type, 8>), grid, block, 0, s, kp);
+                });
             }
         } else if (vec_ok) {
             const int lanes = F / VECW;
@@ -1395,12 +1370,12 @@ int spmm_typed(const gcn_csr_plan *plan, KParams &kp, hipStream_t s)
                 launch_wide<T, VECW>(kp, is64, grid, s);
             } else {
                 dim3 grid(nblk, 1);
-                launch_narrow_lpr<T, VECW>(kp, is64, next_pow2(lanes), grid, s);
+                launch_narrow<T, VECW>(kp, is64, next_pow2(lanes), grid, s);
             }
         } else {
             const int lpr = std::min(kWave, next_pow2(F));
             dim3 grid(nblk, (unsigned)((F + lpr - 1) / lpr));
-            launch_narrow_lpr<T, 1>(kp, is64, lpr, grid, s);
+            launch_narrow<T, 1>(kp, is64, lpr, grid, s);
         }
         if (int rc = launched("spmm launch")) return rc;
     }
@@ -1578,12 +1553,10 @@ int gcn_plan_count_host(const void *rowptr_host, int rowptr_is64, int64_t n_rows
         return fail(GCN_E_BADARG, "gcn_plan_count_host: bad rowptr / n_rows");
     if (item_cost <= 0) item_cost = kDefaultItemCost;
     if (long_thresh <= 0) long_thresh = kDefaultLongThresh;
-    int rc = rowptr_is64
-                 ? plan_walk((const int64_t *)rowptr_host, n_rows, item_cost, long_thresh, nullptr,
-                             0, nullptr, nullptr, 0, nullptr, nullptr, 0, n_items, n_chunks, n_long)
-                 : plan_walk((const int32_t *)rowptr_host, n_rows, item_cost, long_thresh, nullptr,
-                             0, nullptr, nullptr, 0, nullptr, nullptr, 0, n_items, n_chunks,
-                             n_long);
+    int rc = pick_index(rowptr_is64 != 0, [&](auto i) {
+        return plan_walk((const typename decltype(i)::type *)rowptr_host, n_rows, item_cost, long_thresh, nullptr, 0,
+                         nullptr, nullptr, 0, nullptr, nullptr, 0, n_items, n_chunks, n_long);
+    });
     return rc ? fail(rc, "gcn_plan_count_host: rowptr is not monotone") : 0;
 }
 
@@ -1598,12 +1571,10 @@ int gcn_plan_fill_host(const void *rowptr_host, int rowptr_is64, int64_t n_rows,
     if (item_cost <= 0) item_cost = kDefaultItemCost;
     if (long_thresh <= 0) long_thresh = kDefaultLongThresh;
     int64_t ni = 0, nc = 0, nl = 0;
-    int rc = rowptr_is64 ? plan_walk((const int64_t *)rowptr_host, n_rows, item_cost, long_thresh,
-                                     items, n_items, chunk_row, chunk_e0, n_chunks, long_row,
-                                     long_chunk0, n_long, &ni, &nc, &nl)
-                         : plan_walk((const int32_t *)rowptr_host, n_rows, item_cost, long_thresh,
-                                     items, n_items, chunk_row, chunk_e0, n_chunks, long_row,
-                                     long_chunk0, n_long, &ni, &nc, &nl);
+    int rc = pick_index(rowptr_is64 != 0, [&](auto i) {
+        return plan_walk((const typename decltype(i)::type *)rowptr_host, n_rows, item_cost, long_thresh, items,
+                         n_items, chunk_row, chunk_e0, n_chunks, long_row, long_chunk0, n_long, &ni, &nc, &nl);
+    });
     if (rc) return fail(rc, "gcn_plan_fill_host: output arrays too small or rowptr not monotone");
     if (ni != n_items || nc != n_chunks || nl != n_long)
         return fail(GCN_E_CAPACITY, "gcn_plan_fill_host: sizes differ from gcn_plan_count_host");
@@ -1695,8 +1666,10 @@ static int spmm_csr_impl(const gcn_csr_plan *plan, int dtype, const void *B, int
         return fail(GCN_E_BADARG, "gcn_spmm_csr_ep: log_softmax cannot be combined with relu / dropout");
     kp.n_cols = (int32_t)std::min<int64_t>(plan->n_cols, INT32_MAX);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == GCN_DTYPE_F32) return spmm_typed<float, 4>(plan, kp, s);
-    return spmm_typed<bf16_t, 8>(plan, kp, s);
+    return pick_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        return spmm_typed<T, Lane<T>::V>(plan, kp, s);
+    });
 }
 
 int gcn_spmm_csr_ep(const gcn_csr_plan *plan, int dtype, const void *B, int64_t ldb, void *C,
@@ -1734,50 +1707,27 @@ int gcn_relu_dropout_backward(int dtype, const void *grad_out, const void *out, 
     if (n_elems == 0) return 0;
     if (grad_out == nullptr || out == nullptr || grad_pre == nullptr)
         return fail(GCN_E_BADARG, "gcn_relu_dropout_backward: NULL pointer");
-    const int64_t per = dtype == GCN_DTYPE_F32 ? 4 : 8;           // elements per 16-byte lane
+    const int64_t per = lane_elems(dtype);
     const bool vec = (n_elems % per == 0) && (((uintptr_t)grad_out | (uintptr_t)out |
                                                 (uintptr_t)grad_pre) % 16 == 0);
     const int64_t n_units = vec ? n_elems / per : n_elems;
     const unsigned blocks = (unsigned)std::min<int64_t>((n_units + 255) / 256, 256 * 8 * 4);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == GCN_DTYPE_F32) {
-        if (vec)
-            hipLaunchKernelGGL((relu_dropout_bwd_kernel<float, 4>), dim3(blocks), dim3(256), 0, s,
-                               (const float *)grad_out, (const float *)out, (float *)grad_pre,
-                               n_units, scale);
-        else
-            hipLaunchKernelGGL((relu_dropout_bwd_kernel<float, 1>), dim3(blocks), dim3(256), 0, s,
-                               (const float *)grad_out, (const float *)out, (float *)grad_pre,
-                               n_units, scale);
-    } else {
-        if (vec)
-            hipLaunchKernelGGL((relu_dropout_bwd_kernel<bf16_t, 8>), dim3(blocks), dim3(256), 0, s,
-                               (const bf16_t *)grad_out, (const bf16_t *)out, (bf16_t *)grad_pre,
-                               n_units, scale);
-        else
-            hipLaunchKernelGGL((relu_dropout_bwd_kernel<bf16_t, 1>), dim3(blocks), dim3(256), 0, s,
-                               (const bf16_t *)grad_out, (const bf16_t *)out, (bf16_t *)grad_pre,
-                               n_units, scale);
-    }
+    pick_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        pick_int<Lane<T>::V, 1>(vec ? Lane<T>::V : 1, [&](auto v) {
+            hipLaunchKernelGGL((relu_dropout_bwd_kernel<T, decltype(v)::value>), dim3(blocks), dim3(256), 0, s,
+                               (const T *)grad_out, (const T *)out, (T *)grad_pre, n_units, scale);
+        });
+    });
     return launched("relu_dropout_backward launch");
-}
-
-static constexpr int64_t kColsumBlocks = 2048;   // slabs of rows = partial column sums
-
-static bool colsum_shape_ok(int64_t F, int dtype)
-{
-    const int64_t v = dtype == GCN_DTYPE_BF16 ? 8 : 4;   // elements per 16-byte lane
-    return F >= v && F <= 256 * v && (F % v) == 0 && (256 % (F / v)) == 0;
 }
 
 size_t gcn_bwd_colsum_workspace_bytes(int64_t n_rows, int64_t F, int dtype)
 {
-    if (n_rows <= 0 || (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16) ||
-        !colsum_shape_ok(F, dtype))
-        return 0;
-    const int64_t blocks = std::min<int64_t>((n_rows + 63) / 64, kColsumBlocks);
+    if (n_rows <= 0 || !lane_width_ok(F, dtype)) return 0;
     // partial column sums + one byte per row (staging for the row bitmap)
-    return (size_t)blocks * (size_t)F * sizeof(float) + (((size_t)n_rows + 15) & ~(size_t)15);
+    return (size_t)RowSlabs(n_rows).blocks * (size_t)F * sizeof(float) + (((size_t)n_rows + 15) & ~(size_t)15);
 }
 
 static int bwd_colsum_impl(const char *who, int mode, int dtype, const void *grad_out, const void *out,
@@ -1786,26 +1736,21 @@ static int bwd_colsum_impl(const char *who, int mode, int dtype, const void *gra
                            void *workspace, size_t workspace_bytes, void *stream,
                            const int64_t *target = nullptr, const float *coef = nullptr)
 {
-    char msg[160];
-    auto bad = [&](int code, const char *what) {
-        std::snprintf(msg, sizeof msg, "%s: %s", who, what);
-        return fail(code, msg);
-    };
-    if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16) return bad(GCN_E_BADARG, "unknown dtype");
+    if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16) return bad(who, GCN_E_BADARG, "unknown dtype");
     if ((row_bits == nullptr) != (nnz_rows == nullptr))
-        return bad(GCN_E_BADARG, "row_bits and nnz_rows go together");
-    const int64_t vec = dtype == GCN_DTYPE_BF16 ? 8 : 4;
-    if (n_rows < 0 || !colsum_shape_ok(F, dtype))
-        return bad(GCN_E_BADARG, "F must be a multiple of the 16-byte lane width with F/width dividing 256");
+        return bad(who, GCN_E_BADARG, "row_bits and nnz_rows go together");
+    const int64_t vec = lane_elems(dtype);
+    if (n_rows < 0 || !lane_width_ok(F, dtype))
+        return bad(who, GCN_E_BADARG, "F must be a multiple of the 16-byte lane width with F/width dividing 256");
     if (mode >= 2 && F / vec > 64)
-        return bad(GCN_E_BADARG, "a row must fit one wavefront (F / lane width <= 64)");
+        return bad(who, GCN_E_BADARG, "a row must fit one wavefront (F / lane width <= 64)");
     if (row_bits != nullptr && F / vec > 64)   // a row spans several wavefronts: no per-row ballot
-        return bad(GCN_E_BADARG, "row_bits / nnz_rows need F / lane width <= 64 (pass NULL for wider rows)");
+        return bad(who, GCN_E_BADARG, "row_bits / nnz_rows need F / lane width <= 64 (pass NULL for wider rows)");
     if (skip_zero_rows && (row_bits == nullptr || mode == 0))
-        return bad(GCN_E_BADARG, "skip_zero_rows needs the row bitmap outputs and a result tensor");
+        return bad(who, GCN_E_BADARG, "skip_zero_rows needs the row bitmap outputs and a result tensor");
     if (colsum == nullptr || (grad_out == nullptr && mode != 3) || (out != nullptr && grad_pre == nullptr)
         || (mode == 3 && (target == nullptr || coef == nullptr || out == nullptr)))
-        return bad(GCN_E_BADARG, "NULL pointer");
+        return bad(who, GCN_E_BADARG, "NULL pointer");
     hipStream_t s = (hipStream_t)stream;
     if (nnz_rows != nullptr) {
         hipError_t e = hipMemsetAsync(nnz_rows, 0, sizeof(int32_t), s);
@@ -1816,33 +1761,24 @@ static int bwd_colsum_impl(const char *who, int mode, int dtype, const void *gra
         return e == hipSuccess ? 0 : fail_hip(e, who);
     }
     const size_t need = gcn_bwd_colsum_workspace_bytes(n_rows, F, dtype);
-    if (workspace == nullptr || workspace_bytes < need) return bad(GCN_E_WORKSPACE, "workspace too small");
+    if (workspace == nullptr || workspace_bytes < need) return bad(who, GCN_E_WORKSPACE, "workspace too small");
     if (((uintptr_t)grad_out | (uintptr_t)out | (uintptr_t)grad_pre | (uintptr_t)workspace) % 16 != 0)
-        return bad(GCN_E_ALIGN, "16-byte alignment required");
-    const int64_t blocks = std::min<int64_t>((n_rows + 63) / 64, kColsumBlocks);
-    const int rows_per_block = (int)((n_rows + blocks - 1) / blocks);
-    uint8_t *row_nonzero = row_bits ? (uint8_t *)workspace + (size_t)blocks * (size_t)F * sizeof(float)
+        return bad(who, GCN_E_ALIGN, "16-byte alignment required");
+    const RowSlabs sl(n_rows);
+    uint8_t *row_nonzero = row_bits ? (uint8_t *)workspace + (size_t)sl.blocks * (size_t)F * sizeof(float)
                                     : nullptr;
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid((unsigned)sl.blocks), block(256);
     float *part = (float *)workspace;
-#define GCN_LAUNCH_COLSUM(T, V, M)                                                                   \
-    hipLaunchKernelGGL((bwd_colsum_kernel<T, V, M>), grid, block, 0, s, (const T *)grad_out,         \
-                       (const T *)out, (T *)grad_pre, part, n_rows, (int)F, scale, rows_per_block,   \
-                       row_nonzero, nnz_rows, skip_zero_rows ? 1 : 0, target, coef)
-    if (dtype == GCN_DTYPE_F32) {
-        if (mode == 3) GCN_LAUNCH_COLSUM(float, 4, 3);
-        else if (mode == 2) GCN_LAUNCH_COLSUM(float, 4, 2);
-        else if (mode == 1) GCN_LAUNCH_COLSUM(float, 4, 1);
-        else GCN_LAUNCH_COLSUM(float, 4, 0);
-    } else {
-        if (mode == 3) GCN_LAUNCH_COLSUM(bf16_t, 8, 3);
-        else if (mode == 2) GCN_LAUNCH_COLSUM(bf16_t, 8, 2);
-        else if (mode == 1) GCN_LAUNCH_COLSUM(bf16_t, 8, 1);
-        else GCN_LAUNCH_COLSUM(bf16_t, 8, 0);
-    }
-#undef GCN_LAUNCH_COLSUM
+    pick_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        pick_int<0, 1, 2, 3>(mode, [&](auto m) {
+            hipLaunchKernelGGL((bwd_colsum_kernel<T, Lane<T>::V, decltype(m)::value>), grid, block, 0, s,
+                               (const T *)grad_out, (const T *)out, (T *)grad_pre, part, n_rows, (int)F, scale,
+                               sl.rows_per_block, row_nonzero, nnz_rows, skip_zero_rows ? 1 : 0, target, coef);
+        });
+    });
     hipLaunchKernelGGL(colsum_finish_kernel, dim3((unsigned)((F + 31) / 32)), dim3(1024), 0, s,
-                       (const float *)workspace, colsum, (int)blocks, (int)F);
+                       (const float *)workspace, colsum, (int)sl.blocks, (int)F);
     if (row_bits != nullptr)
         hipLaunchKernelGGL(pack_row_flags_kernel, dim3((unsigned)((((n_rows + 31) >> 5) + 255) / 256)),
                            dim3(256), 0, s, (const uint8_t *)row_nonzero, row_bits, n_rows);
@@ -1916,24 +1852,19 @@ int gcn_sddmm_csr(const gcn_csr_plan *plan, int dtype, const void *G, int64_t ld
     sp.n_chunks = (int32_t)plan->n_chunks;
     sp.long_thresh = plan->long_thresh > 0 ? plan->long_thresh : kDefaultLongThresh;
     const bool is64 = plan->rowptr_is64 != 0;
-    const size_t es = dtype == GCN_DTYPE_BF16 ? 2 : 4;
-    const int64_t vw = dtype == GCN_DTYPE_BF16 ? 8 : 4;
+    const int64_t vw = lane_elems(dtype), es = 16 / vw;
     const bool vec_ok = (F % vw == 0) && (((uintptr_t)G | (uintptr_t)B) % 16 == 0) &&
-                        ((ldg * (int64_t)es) % 16 == 0) && ((ldb * (int64_t)es) % 16 == 0);
+                        ((ldg * es) % 16 == 0) && ((ldb * es) % 16 == 0);
     const dim3 grid((unsigned)((sp.n_total + kWavesPerBlock - 1) / kWavesPerBlock)), block(kWave * kWavesPerBlock);
-#define GCN_LAUNCH_SDDMM(T, V)                                                             \
-    do {                                                                                   \
-        if (is64) hipLaunchKernelGGL((sddmm_kernel<T, V, int64_t>), grid, block, 0, s, sp); \
-        else hipLaunchKernelGGL((sddmm_kernel<T, V, int32_t>), grid, block, 0, s, sp);      \
-    } while (0)
-    if (dtype == GCN_DTYPE_F32) {
-        if (vec_ok) GCN_LAUNCH_SDDMM(float, 4);
-        else GCN_LAUNCH_SDDMM(float, 1);
-    } else {
-        if (vec_ok) GCN_LAUNCH_SDDMM(bf16_t, 8);
-        else GCN_LAUNCH_SDDMM(bf16_t, 1);
-    }
-#undef GCN_LAUNCH_SDDMM
+    pick_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        pick_int<Lane<T>::V, 1>(vec_ok ? Lane<T>::V : 1, [&](auto v) {
+            pick_index(is64, [&](auto i) {
+                hipLaunchKernelGGL((sddmm_kernel<T, decltype(v)::value, typename decltype(i)::type>), grid, block, 0,
+                                   s, sp);
+            });
+        });
+    });
     return launched("gcn_sddmm_csr launch");
 }
 
@@ -1943,8 +1874,10 @@ int gcn_csr_transpose_host(const void *rowptr_host, int rowptr_is64, const int32
 {
     if (rowptr_host == nullptr || rowptr_t == nullptr || n_rows < 0 || n_cols < 0)
         return fail(GCN_E_BADARG, "gcn_csr_transpose_host: bad arguments");
-    auto run = [&](auto *rp, auto *rpt) -> int {
-        typedef typename std::remove_pointer<decltype(rpt)>::type I;
+    int rc = pick_index(rowptr_is64 != 0, [&](auto i) -> int {
+        typedef typename decltype(i)::type I;
+        const I *rp = (const I *)rowptr_host;
+        I *rpt = (I *)rowptr_t;
         const int64_t nnz = (int64_t)rp[n_rows];
         if (nnz > 0 && (col == nullptr || val == nullptr || col_t == nullptr || val_t == nullptr))
             return GCN_E_BADARG;
@@ -1964,9 +1897,7 @@ int gcn_csr_transpose_host(const void *rowptr_host, int rowptr_is64, const int32
         for (int64_t k = n_cols; k > 0; --k) rpt[k] = rpt[k - 1];
         rpt[0] = (I)0;
         return 0;
-    };
-    int rc = rowptr_is64 ? run((const int64_t *)rowptr_host, (int64_t *)rowptr_t)
-                         : run((const int32_t *)rowptr_host, (int32_t *)rowptr_t);
+    });
     return rc ? fail(rc, "gcn_csr_transpose_host: column index out of range or NULL array") : 0;
 }
 

@@ -192,17 +192,12 @@ int gcn_sym_normalize_device(const void *rowptr, int rowptr_is64, const int32_t 
     double *deg = (double *)workspace;
     const unsigned blocks = (unsigned)std::min<int64_t>((n_rows + 3) / 4, 256 * 64);
     hipStream_t s = (hipStream_t)stream;
-    if (rowptr_is64) {
-        hipLaunchKernelGGL(sym_degree_kernel<int64_t>, dim3(blocks), dim3(256), 0, s, (const int64_t *)rowptr, val,
-                           n_rows, deg);
-        hipLaunchKernelGGL(sym_scale_kernel<int64_t>, dim3(blocks), dim3(256), 0, s, (const int64_t *)rowptr, col,
-                           val, n_rows, deg);
-    } else {
-        hipLaunchKernelGGL(sym_degree_kernel<int32_t>, dim3(blocks), dim3(256), 0, s, (const int32_t *)rowptr, val,
-                           n_rows, deg);
-        hipLaunchKernelGGL(sym_scale_kernel<int32_t>, dim3(blocks), dim3(256), 0, s, (const int32_t *)rowptr, col,
-                           val, n_rows, deg);
-    }
+    pick_index(rowptr_is64 != 0, [&](auto i) {
+        typedef typename decltype(i)::type I;
+        hipLaunchKernelGGL(sym_degree_kernel<I>, dim3(blocks), dim3(256), 0, s, (const I *)rowptr, val, n_rows, deg);
+        hipLaunchKernelGGL(sym_scale_kernel<I>, dim3(blocks), dim3(256), 0, s, (const I *)rowptr, col, val, n_rows,
+                           deg);
+    });
     return launched(kNorm);
 }
 

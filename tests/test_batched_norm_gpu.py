@@ -295,6 +295,24 @@ def test_pool_forward_backward_fp32(n_name, c, k):
         assert_parity(a.numpy(), r32.numpy(), r64.numpy(), f"{name} [{k}x{n}x{c}]")
 
 
+@pytest.mark.parametrize("n_name", ["1", "n_big"])
+def test_pool_forward_backward_bf16(n_name):
+    """bf16 storage: the bf16 instantiations of the two pool sweeps.  The sums are exact products added in double,
+    so pooled and dh are the float64 results on the bf16-rounded inputs with ONE rounding to bf16 each (dh: after
+    the fp32 quotient g / count) — within one bf16 ulp, 2^-8 relative, of float64; a zero stays zero."""
+    c, k = 128, 3
+    n = rows_of(n_name, c, torch.bfloat16)
+    h, cot = seeded((k, n, c), 131).bfloat16(), seeded((k, c), 132).bfloat16()
+    mask = bernoulli_mask(k, n, 133)
+    mask[:, 0] = 1.0
+    count = (mask != 0).sum(1)
+    got = hip_pool(h, mask, None, cot)
+    ref64 = pool_ref(h.float(), mask, count, cot.float(), torch.float64)
+    for name, a, r64 in zip(("pooled", "dh"), got, ref64):
+        assert a.dtype == torch.bfloat16 and a.shape == r64.shape
+        assert bool(((a.double() - r64).abs() <= 2.0 ** -8 * r64.abs()).all()), f"bf16 {name} [{k}x{n}x{c}]"
+
+
 def test_pool_with_the_forks_count_and_an_empty_sample():
     """count = sample 0's vertex count for every sample (reference pygcn/models.py:279); a sample whose
     mask is all zero under its OWN count is 0 / 0: torch's NaN pattern."""

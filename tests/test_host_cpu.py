@@ -135,6 +135,15 @@ def test_transpose_host_matches_oracle(oracle):
     np.testing.assert_array_equal(rpt, o_rp)
     np.testing.assert_array_equal(ct, o_c)
     np.testing.assert_array_equal(vt, o_v)
+    # the int64 form of both row pointers: the same transpose
+    rp64, rpt64 = a.rowptr.astype(np.int64), np.zeros(91, np.int64)
+    ct64, vt64 = np.zeros(a.nnz, np.int32), np.zeros(a.nnz, np.float32)
+    rc = L.gcn_csr_transpose_host(rp64.ctypes.data, 1, a.col.ctypes.data, a.val.ctypes.data,
+                                  60, 90, rpt64.ctypes.data, ct64.ctypes.data, vt64.ctypes.data)
+    assert rc == 0
+    np.testing.assert_array_equal(rpt64, o_rp)
+    np.testing.assert_array_equal(ct64, ct)
+    np.testing.assert_array_equal(vt64, vt)
 
 
 def test_module_surface_matches_reference():
@@ -430,3 +439,47 @@ def test_needs_build_watches_the_internal_header(monkeypatch):
         assert build.needs_build(), d
         mtimes[d] = 1000.0
     assert not build.needs_build()
+
+
+def test_internal_header_picks_in_a_standalone_host_program(tmp_path):
+    """tests/c_abi/pick_check.cpp checks pick_dtype / pick_index / pick_int of pygcn_amd/csrc/gcn_internal.h (and the
+    slab rules beside them).  A plain host executable with its own main, built host-only under the address and
+    undefined-behaviour sanitizers: it needs neither the library nor a device."""
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    exe = str(tmp_path / "pick_check")
+    subprocess.check_call([hipcc, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-Wall", "-Werror",
+                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "pygcn_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "c_abi", "pick_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "pick_check ok" in out.stdout
+
+
+def test_workspace_queries_answer_as_recorded():
+    """Every *_workspace_bytes query answers what tests/golden/workspace_bytes.json recorded from the library of
+    commit 8f70753 (tools/record_workspace_bytes.py): the sizes are ABI-visible and follow the slab rules, so a change
+    to either shows here.  The grid has the slab edges (64 rows, the 2048-slab cap, the int32 bound), widths the lane
+    rule takes and refuses at either dtype, an unknown dtype, and batch 0 / 1 / 65535 / 65536.  The three queries that
+    add hipCUB's temporary-storage size (planner, transpose, COO ingest) are held where hipCUB is not asked: it sizes
+    that storage for the device it finds, so those answers differ between a machine with a device and one without.
+    Queries only: nothing launches."""
+    import json
+    golden = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "workspace_bytes.json")))
+    queries = sorted(n for n in _native.SIGNATURES if n.endswith("_workspace_bytes"))
+    assert sorted(golden) == queries, set(golden) ^ set(queries)
+    L = _native.lib()
+    differ = []
+    for name, rows in golden.items():
+        assert rows, name
+        for *args, want in rows:
+            if name == "gcn_spmm_workspace_bytes":           # (its first column is the plan's n_chunks)
+                plan = _native.GcnCsrPlan()
+                plan.n_chunks = args[0]
+                args = [ctypes.byref(plan)] + args[1:]
+            got = int(getattr(L, name)(*args))
+            if got != want:
+                differ.append((name, args, got, want))
+    assert not differ, differ[:20]

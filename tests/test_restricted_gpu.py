@@ -147,7 +147,17 @@ def test_take_rows_equals_scipy(dev, which, rowptr_dtype):
     # without a map: scipy's row selection keeps the stored order
     t = g.take_rows(rows_t)
     same(t, A[rows])
-    if len(rows):       # its own schedule (the 300-entry row is chunked): the product runs on it
+    if len(rows):
+        # the 64-bit form of the OUTPUT row pointer (the wrapper takes it only past 2^31 entries): the same entries.
+        # With rowptr_dtype this is all four (input, output) widths of gcn_csr_take_rows.
+        from pygcn_amd import _native
+        rp64 = t.rowptr.to(torch.int64)
+        col64, val64 = torch.full_like(t.col, -1), torch.full_like(t.val, -1.0)
+        _native.launch("gcn_csr_take_rows", dev, g.rowptr.data_ptr(), int(rowptr_dtype == torch.int64), g.col.data_ptr(),
+                       g.val.data_ptr(), rows_t.data_ptr(), len(rows), None, rp64.data_ptr(), 1, col64.data_ptr(),
+                       val64.data_ptr(), None)
+        assert t.rowptr.dtype == torch.int32 and torch.equal(col64, t.col) and torch.equal(val64, t.val)
+        # its own schedule (the 300-entry row is chunked): the product runs on it
         assert_normwise(S.spmm_csr(t, B).cpu(), A[rows].astype(np.float64) @ B.cpu().numpy().astype(np.float64),
                         TOL, "product on the taken rows")
     # with a map: the columns that occur in the selected rows, numbered by position (a monotone map keeps every
