@@ -90,7 +90,9 @@ typedef struct gcn_csr_plan {
  * gcn_csr_take_rows (dropout keyed by a row list and row blocks of a CSR matrix, for the forward pass restricted
  * to the loss rows' receptive field).  Also additive to 26: gcn_bn_linear_workspace_bytes / gcn_bn_linear_forward /
  * gcn_bn_linear_backward_sums / gcn_bn_linear_backward_apply (ReLU + BatchNorm folded into the next layer's X·W for
- * 32-wide layers).
+ * 32-wide layers).  Also additive to 26: gcn_agg_linear_partial_rows / gcn_agg_linear_forward /
+ * gcn_agg_linear_backward (the dense half of an aggregate-first input layer, (A·X)·W + b, for inputs of 4 .. 32
+ * columns into a 32-wide layer).
  * 25 (round 4, late): new entry point gcn_gemm_atg256_f32_b3_colsum (the
  * weight gradient with the bias gradient Σ G[rows] as a side result); gcn_gemm_atg256_workspace_bytes grew by
  * 1 KiB per workgroup; struct gcn_gemm_epilogue gained keep_bits_out / mask_bits at its END (zero them);
@@ -979,6 +981,47 @@ int gcn_sym_normalize_device(const void *rowptr, int rowptr_is64, const int32_t 
 int gcn_csr_mirror_device(const int32_t *rowptr, const int32_t *col, const float *val, int64_t n_rows, int64_t nnz,
                           int32_t *mirror, int64_t *counts, void *stream);
 int gcn_gather_f32(const float *src, const int32_t *index, int64_t n, int64_t src_len, float *out, void *stream);
+
+/*
+ * The dense half of an AGGREGATE-FIRST input layer, (A·X)·W + b, for narrow inputs (pygcn_amd/csrc/gcn_agglin.hip):
+ * the fork's models feed 4, 8 or 16 columns into a 32-wide GCN (reference pygcn/gnn-over-mlp.py:221-237,
+ * policy-generator.py:330-350) and layer 1's input needs no gradient, so with z = A·X formed by gcn_spmm_csr on
+ * Fin-wide rows, the layer and its parameter gradients are two dense sweeps.  z is contiguous fp32
+ * [n_rows, batch * Fin], y and g contiguous fp32 [n_rows, batch * Fout]: batch samples side by side, sample j in the
+ * columns [j * F, (j + 1) * F) — so row r, sample j is "unit" u = r * batch + j, Fin contiguous floats of z and
+ * Fout contiguous floats of y.  weight is fp32 [Fin, Fout] row-major (GraphConvolution's), bias fp32 [Fout] or NULL.
+ *   gcn_agg_linear_forward    y[r, j * Fout + c] = act(sum_i z[r, j * Fin + i] * weight[i, c] + bias[c]).  THE ORDER,
+ *                             per element, in fp32: acc = fmaf(z_0, W[0][c], 0); acc = fmaf(z_i, W[i][c], acc) for
+ *                             i = 1 .. Fin - 1 ascending; then acc + bias[c] (skipped when bias is NULL); then, with
+ *                             relu, acc < 0 ? 0 : acc (NaN stays NaN).  No sum mixes units: a sample's y is bitwise
+ *                             that of the batch = 1 call on a contiguous copy of its columns.
+ *   gcn_agg_linear_backward   with gp = relu ? (y <= 0 ? 0 : g) : g  (y: the forward result; NULL allowed without
+ *                             relu):  grad_w[i, c] = sum_r sum_j z[r, j * Fin + i] * gp[r, j * Fout + c]  (fp32
+ *                             [Fin, Fout]),  grad_b[c] = sum_r sum_j gp[r, j * Fout + c]  (fp32 [Fout], or NULL: not
+ *                             formed).  Two stages, all sums in DOUBLE: block b of the sweep owns the units
+ *                             [b * R, min((b + 1) * R, M)), its wavefront w the units [b * R + 16 * P * w,
+ *                             b * R + 16 * P * (w + 1)) of them; a lane owns one column and the wavefront's units of
+ *                             one parity, ascending; the two parities are added, then the 4 wavefronts in order, into
+ *                             row b of `partials` (Fin * Fout doubles of grad_w row-major, then Fout of grad_b).  The
+ *                             finishing launch adds the rows in block order 0, 1, ... and rounds once to fp32.  No
+ *                             atomics: bitwise reproducible, whichever block ran first.  g, z (and y) are read once.
+ * There is no input-gradient sweep: a layer whose input needs a gradient is evaluated as A·(X·W).
+ * SHAPE RULE: 1 <= n_rows <= 2^40, Fin in {4, 8, ..., 32}, Fout = 32, 1 <= batch <= 65535 (else GCN_E_BADARG, as a
+ * NULL z, weight, y / g, grad_w, or y with relu); z, y, g, weight and bias 16-byte aligned, grad_w and grad_b 4-byte,
+ * partials 8-byte (GCN_E_ALIGN).
+ * Scratch of gcn_agg_linear_backward: `partials`, DEVICE double [partial_rows][Fin * Fout + Fout], allocated by the
+ * caller (NULL, or partial_rows below the query: GCN_E_WORKSPACE), with
+ *     gcn_agg_linear_partial_rows = B,
+ *     M = n_rows * batch,  P = ceil(M / (64 * 2048)),  R = 64 * P,  B = ceil(M / R)  (<= 2048)
+ * and 0 outside the shape rule.
+ * (ABI 26, additive.)
+ */
+int64_t gcn_agg_linear_partial_rows(int64_t n_rows, int64_t Fin, int64_t Fout, int64_t batch);
+int gcn_agg_linear_forward(const float *z, const float *weight, const float *bias, float *y, int64_t n_rows,
+                           int64_t Fin, int64_t Fout, int64_t batch, int relu, void *stream);
+int gcn_agg_linear_backward(const float *g, const float *y, const float *z, int64_t n_rows, int64_t Fin,
+                            int64_t Fout, int64_t batch, int relu, float *grad_w, float *grad_b, double *partials,
+                            int64_t partial_rows, void *stream);
 
 #ifdef __cplusplus
 }

@@ -150,6 +150,9 @@ SIGNATURES = {
     "gcn_sym_normalize_device": (i, [p, i, p, p, i64, p, sz, p]),
     "gcn_csr_mirror_device": (i, [p, p, p, i64, i64, p, p, p]),
     "gcn_gather_f32": (i, [p, p, i64, i64, p, p]),
+    "gcn_agg_linear_partial_rows": (i64, [i64, i64, i64, i64]),
+    "gcn_agg_linear_forward": (i, [p, p, p, p, i64, i64, i64, i64, i, p]),
+    "gcn_agg_linear_backward": (i, [p, p, p, i64, i64, i64, i64, i, p, p, p, i64, p]),
 }
 EXPORTS = tuple(SIGNATURES)
 

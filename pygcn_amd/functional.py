@@ -33,6 +33,9 @@ from pygcn_amd.head import vertex_mlp  # noqa: E402,F401
 # apply_bn(F.relu(.)) folded into the next layer's torch.mm(input, weight) (pygcn/models.py:49-56, layers.py:33) for
 # its 32-wide layers, the normalised activation never written: pygcn_amd/normlin.py
 from pygcn_amd.normlin import relu_batch_norm_linear  # noqa: E402,F401
+# its narrow input layers (4, 8 or 16 columns into 32: pygcn/gnn-over-mlp.py:221-237, policy-generator.py:330-350)
+# evaluated aggregate-first, (adj·x)·W + b, where the input needs no gradient: pygcn_amd/agglin.py
+from pygcn_amd.agglin import aggregate_linear  # noqa: E402,F401
 
 
 class NLLGrad(torch.Tensor):

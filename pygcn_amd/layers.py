@@ -157,6 +157,17 @@ class GraphConvolution(Module):
         support = DenseMMFunction.apply(wide.reshape(n * k, self.in_features), self.weight)
         return self._aggregate_wide(support.view(n, k * self.out_features), adj, k, relu)
 
+    def forward_aggregate_first(self, wide, adj, k=None, relu=False):
+        """The layer as an INPUT layer, evaluated as (adj · wide) · W + bias where `functional.aggregate_linear`
+        takes the call (a CSRGraph, 4 .. 32 input columns into 32, an input that needs no gradient): the sparse
+        product gathers k·Fin floats per entry instead of k·Fout, and the backward pass has none.  wide is
+        [N, k·Fin] as in `forward_wide`; k = None is the single-sample call on [N, Fin].  Every call outside the
+        rule IS the default one: `forward_wide(wide, adj, k, relu)`, or `forward(wide, adj, relu=relu)` for k = None."""
+        from pygcn_amd import agglin
+        if wide.dim() == 2 and agglin.supported(wide, adj, self.weight, self.bias, k or 1):
+            return agglin.aggregate_linear(wide, adj, self.weight, self.bias, batch=k or 1, relu=relu)
+        return self.forward(wide, adj, relu=relu) if k is None else self.forward_wide(wide, adj, k, relu)
+
     def __repr__(self):
         return self.__class__.__name__ + ' (' \
                + str(self.in_features) + ' -> ' \

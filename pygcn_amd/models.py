@@ -136,18 +136,27 @@ class GCN(nn.Module):
 
 class GCNStack(nn.Module):
     """k x (GraphConvolution + ReLU), the shape of the fork's GeneratorGCN
-    (reference pygcn/models.py:74-124: gc1..gc3, ReLU after each, no BatchNorm)."""
+    (reference pygcn/models.py:74-124: gc1..gc3, ReLU after each, no BatchNorm).
 
-    def __init__(self, nfeat, nhid, nclass, dropout=0.0, nlayers=3):
+    `aggregate_first=True` (opt-in): layer 1 only runs as `GraphConvolution.forward_aggregate_first` —
+    (adj·x)·W + b with the ReLU in the sweep, where `functional.aggregate_linear` takes the call, the default
+    layer everywhere else.  Parameters and state_dict keys do not change."""
+
+    def __init__(self, nfeat, nhid, nclass, dropout=0.0, nlayers=3, aggregate_first=False):
         super(GCNStack, self).__init__()
         dims = [nfeat] + [nhid] * (nlayers - 1) + [nclass]
         for i in range(nlayers):
             setattr(self, f"gc{i + 1}", GraphConvolution(dims[i], dims[i + 1]))
         self.nlayers = nlayers
         self.dropout = dropout
+        self.aggregate_first = bool(aggregate_first)
 
     def forward(self, x, adj):
-        for i in range(self.nlayers):
+        first = 0
+        if self.aggregate_first and x.dim() == 2:
+            x = self.gc1.forward_aggregate_first(x, adj, relu=True)       # (ReLU inside the sweep)
+            first = 1
+        for i in range(first, self.nlayers):
             x = getattr(self, f"gc{i + 1}")(x, adj, relu=True)
         return x
 
@@ -175,9 +184,15 @@ class GCNBatchNorm(nn.Module):
     `functional.relu_batch_norm_linear` — the normalised activation is neither written nor kept for the
     backward pass — and aggregate its result (GraphConvolution.aggregate); layer 1 is unchanged.  The HIP
     sweeps carry 32 -> 32 layers (the fork's widths); other widths run the same composition of nodes as the
-    default.  Parameters and state_dict keys do not change."""
+    default.  Parameters and state_dict keys do not change.
 
-    def __init__(self, nfeat, nhid, nclass, dropout, NN=None, fused_norm=False):
+    `aggregate_first=True` (opt-in): layer 1 ONLY is evaluated as (adj·x)·W + b,
+    `GraphConvolution.forward_aggregate_first` — for the fork's narrow inputs (4 .. 32 columns into 32) on a
+    CSRGraph with an input that needs no gradient, the sparse product gathers k·nfeat floats per entry instead of
+    k·nhid and layer 1's backward pass has none; its pre-activation output feeds ReLU + BatchNorm unchanged, so the
+    flag composes with `fused_norm`.  Any other call runs the default layer.  Same parameters, same state_dict."""
+
+    def __init__(self, nfeat, nhid, nclass, dropout, NN=None, fused_norm=False, aggregate_first=False):
         super(GCNBatchNorm, self).__init__()
         self.gc1 = GraphConvolution(nfeat, nhid)
         self.gc2 = GraphConvolution(nhid, nhid)
@@ -185,6 +200,13 @@ class GCNBatchNorm(nn.Module):
         self.dropout = dropout
         self.NN = NN
         self.fused_norm = bool(fused_norm)
+        self.aggregate_first = bool(aggregate_first)
+
+    def _layer1(self, x, adj, k=None):
+        """gc1's pre-activation output on x [N, k·nfeat] (k None: the single sample [N, nfeat])."""
+        if self.aggregate_first:
+            return self.gc1.forward_aggregate_first(x, adj, k)
+        return self.gc1(x, adj) if k is None else self.gc1.forward_wide(x, adj, k)
 
     def forward(self, x, adj):
         if isinstance(adj, ShardedGraph):
@@ -193,8 +215,8 @@ class GCNBatchNorm(nn.Module):
         if x.dim() == 3:
             return self._forward_batched(x, adj)
         if self.fused_norm:
-            return self._fused_tail(self.gc1(x, adj), adj, 1)
-        x = relu_batch_norm(self.gc1(x, adj))
+            return self._fused_tail(self._layer1(x, adj), adj, 1)
+        x = relu_batch_norm(self._layer1(x, adj))
         x = relu_batch_norm(self.gc2(x, adj))
         return self.gc3(x, adj, relu=True)
 
@@ -219,8 +241,8 @@ class GCNBatchNorm(nn.Module):
             raise RuntimeError("GCNBatchNorm: a ShardedGraph adjacency is not supported — BatchNorm's "
                                "statistics run over all vertices, and cross-rank statistics are not built")
         if self.fused_norm:
-            return self._fused_tail(self.gc1.forward_wide(wide, adj, k), adj, k)
-        h = relu_batch_norm(self.gc1.forward_wide(wide, adj, k), batch=k)
+            return self._fused_tail(self._layer1(wide, adj, k), adj, k)
+        h = relu_batch_norm(self._layer1(wide, adj, k), batch=k)
         h = relu_batch_norm(self.gc2.forward_wide(h, adj, k), batch=k)
         return self.gc3.forward_wide(h, adj, k, relu=True)
 
@@ -264,12 +286,14 @@ class SoftGenerator(nn.Module):
 
     The policy step of the fork's driver is here as two methods over pygcn_amd/select.py: `select_action`
     (its `select_action`, reference pygcn/rl-policy-generator.py:324-370) and `log_prob` (its
-    ReplayBuffer.get_log_prob, pygcn/utils.py:516-522), neither with a host synchronisation."""
+    ReplayBuffer.get_log_prob, pygcn/utils.py:516-522), neither with a host synchronisation.
+
+    `aggregate_first=True` (opt-in) is passed on to GCNStack."""
 
     def __init__(self, nfeat, nhid, nclass, dropout, NN, linear_nhid1, linear_nhid2, dim_touched=None,
-                 linear_bias=True):
+                 linear_bias=True, aggregate_first=False):
         super(SoftGenerator, self).__init__()
-        self.GCN = GCNStack(nfeat, nhid, nclass, dropout, nlayers=3)
+        self.GCN = GCNStack(nfeat, nhid, nclass, dropout, nlayers=3, aggregate_first=aggregate_first)
         self.PoolMLP = SoftGeneratorPoolMLP(nclass, linear_nhid1, linear_nhid2, bias=linear_bias)
         self.dim_touched = dim_touched
         self.NN = NN
@@ -354,12 +378,13 @@ class Generator(nn.Module):
     nclass + (columns of x past dim_touched).
 
     `fused_head=True` (opt-in): the MLP runs as `functional.vertex_mlp` — fused HIP sweeps that read the tail of
-    x in place and recompute the hidden activations (pygcn_amd/head.py); same parameters, same state_dict."""
+    x in place and recompute the hidden activations (pygcn_amd/head.py); same parameters, same state_dict.
+    `aggregate_first=True` (opt-in) is passed on to GCNStack: layer 1 as (adj·x)·W + b."""
 
     def __init__(self, nfeat, nhid, nclass, dropout, NN, linear_nin, linear_nhid1, linear_nhid2, dim_touched=None,
-                 linear_nout=1, linear_bias=True, fused_head=False):
+                 linear_nout=1, linear_bias=True, fused_head=False, aggregate_first=False):
         super(Generator, self).__init__()
-        self.GCNLayer = GCNStack(nfeat, nhid, nclass, dropout, nlayers=3)
+        self.GCNLayer = GCNStack(nfeat, nhid, nclass, dropout, nlayers=3, aggregate_first=aggregate_first)
         self.MLPLayers = GeneratorMLPLayers(linear_nin, linear_nhid1, linear_nhid2, linear_nout, bias=linear_bias)
         self.dim_touched = dim_touched
         self.NN = NN
@@ -385,14 +410,14 @@ class Hierarchical_Generator(nn.Module):
     MLPLayers, where the LAST column of x is a group label that does not enter the MLP (:392) and every
     vertex of `target_group` (0, as the fork hard-codes it, :394) gets the minimum score before the flag
     is taken (:395-397) — torch ops on [N], the minimum stays on the device.  `fused_head=True` as in Generator,
-    without BatchNorm and without the label column."""
+    without BatchNorm and without the label column; `aggregate_first=True` as in Generator."""
 
     target_group = 0
 
     def __init__(self, nfeat, nhid, nclass, dropout, NN, linear_nin, linear_nhid1, linear_nhid2, dim_touched=None,
-                 linear_nout=1, linear_bias=True, fused_head=False):
+                 linear_nout=1, linear_bias=True, fused_head=False, aggregate_first=False):
         super(Hierarchical_Generator, self).__init__()
-        self.GCNLayer = GCNStack(nfeat, nhid, nclass, dropout, nlayers=3)
+        self.GCNLayer = GCNStack(nfeat, nhid, nclass, dropout, nlayers=3, aggregate_first=aggregate_first)
         self.MLPLayers = MLPLayers(linear_nin, linear_nhid1, linear_nhid2, linear_nout, bias=linear_bias)
         self.dim_touched = dim_touched
         self.NN = NN
@@ -452,12 +477,14 @@ class GCN_OVER_MLP(nn.Module):
     pygcn/policy-generator.py:398-420), where the flag is the only thing that receives gradient: x stays a
     constant, and layer 1 of the GCN forms no input gradient.
 
-    `fused_norm=True` (opt-in) is passed on to GCNBatchNorm."""
+    `fused_norm=True` and `aggregate_first=True` (both opt-in) are passed on to GCNBatchNorm.  The latter takes
+    effect when x needs no gradient — the flag inside a constant x, or the flag on its own."""
 
     def __init__(self, nfeat, nhid, nclass, dropout, NN, linear_nin, linear_nhid1, linear_nhid2, dim_touched=None,
-                 linear_nout=1, linear_bias=True, fused_norm=False):
+                 linear_nout=1, linear_bias=True, fused_norm=False, aggregate_first=False):
         super(GCN_OVER_MLP, self).__init__()
-        self.GCNLayer = GCNBatchNorm(nfeat, nhid, nclass, dropout, NN, fused_norm=fused_norm)
+        self.GCNLayer = GCNBatchNorm(nfeat, nhid, nclass, dropout, NN, fused_norm=fused_norm,
+                                     aggregate_first=aggregate_first)
         self.PoolLayer = PoolLayer()
         self.MLPLayers = MLPLayers(linear_nin, linear_nhid1, linear_nhid2, linear_nout, bias=linear_bias)
         self.dim_touched = dim_touched
@@ -481,8 +508,8 @@ class GCN_OVER_MLP(nn.Module):
 def get_model(config, model_name='GCN'):
     """The fork's `get_model` (reference pygcn/models.py:440-460): `config` is any object with its attribute
     names — gcn_nfeat, gcn_nhid, gcn_nclass, gcn_dropout, NN, dim_touched, linear_nin, linear_nhid1,
-    linear_nhid2, linear_nout, linear_bias, and optionally fused_head (the two generators' opt-in) and fused_norm
-    (the evaluator's).  'MLP',
+    linear_nhid2, linear_nout, linear_bias, and optionally fused_head (the two generators' opt-in), fused_norm
+    (the evaluator's) and aggregate_first (every model with a GCN).  'MLP',
     'GNN_OVER_MLP', 'Generator', 'Hierarchical_Generator' and 'SoftGenerator' give the classes of this module.
     'GCN', the default, is broken in the fork (it passes six
     arguments to a five-argument GCN, :444: a TypeError) and raises TypeError here too; the fork lets an unknown
@@ -495,17 +522,18 @@ def get_model(config, model_name='GCN'):
         raise ValueError(f"get_model: unknown model name {model_name!r} (MLP, GNN_OVER_MLP, Generator, "
                          "Hierarchical_Generator, SoftGenerator)")
     c = config
+    agg = getattr(c, 'aggregate_first', False)
     gcn = (c.gcn_nfeat, c.gcn_nhid, c.gcn_nclass, c.gcn_dropout, c.NN)
     if model_name == 'MLP':
         return nn.Sequential(PoolLayer(), MLPLayers(c.linear_nin, c.linear_nhid1, c.linear_nhid2, c.linear_nout,
                                                     bias=c.linear_bias))
     if model_name == 'GNN_OVER_MLP':
         return GCN_OVER_MLP(*gcn, c.linear_nin, c.linear_nhid1, c.linear_nhid2, c.dim_touched, c.linear_nout,
-                            c.linear_bias, getattr(c, 'fused_norm', False))
+                            c.linear_bias, getattr(c, 'fused_norm', False), agg)
     if model_name == 'Generator':
         return Generator(*gcn, c.linear_nin, c.linear_nhid1, c.linear_nhid2, c.dim_touched, c.linear_nout,
-                         c.linear_bias, getattr(c, 'fused_head', False))
+                         c.linear_bias, getattr(c, 'fused_head', False), agg)
     if model_name == 'Hierarchical_Generator':
         return Hierarchical_Generator(*gcn, c.linear_nin, c.linear_nhid1, c.linear_nhid2, c.dim_touched,
-                                      c.linear_nout, c.linear_bias, getattr(c, 'fused_head', False))
-    return SoftGenerator(*gcn, c.linear_nhid1, c.linear_nhid2, c.dim_touched, c.linear_bias)
+                                      c.linear_nout, c.linear_bias, getattr(c, 'fused_head', False), agg)
+    return SoftGenerator(*gcn, c.linear_nhid1, c.linear_nhid2, c.dim_touched, c.linear_bias, agg)
