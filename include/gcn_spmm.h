@@ -596,6 +596,29 @@ int gcn_spmm_csr_packed(const gcn_csr_plan *plan, const uint32_t *slots, const f
                         int64_t ldc, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The POOLED 384-byte form (additive to ABI 26): the same row with ONE pool of values, so the padding against a row
+ * denser than the mean is paid once and not once per quarter — three whole 128-byte lines per gathered row.
+ *   slot r = words [96 r, 96 r + 96) of `slots` (contiguous, 16-byte aligned; three whole lines per slot
+ *   at a 128-byte aligned base, which is what the Python side allocates):
+ *   [0 .. 7]   the masks: words 2q, 2q + 1 are quarter q's 64-bit mask, the quarters and bits of the 512-byte form
+ *              (bit 4 cb + j of quarter q <=> column 16 cb + 4 q + j; set <=> the bit pattern is non-zero, so -0.0 is
+ *              a stored value);
+ *   [8]        the header, c_q = the number of set bits of quarter q: byte 0 = c0, byte 1 = c0 + c1, byte 2 = c0 + c1
+ *              + c2 (where quarters 1, 2, 3 begin in the pool), byte 3 = min(c0 + c1 + c2 + c3, 255);
+ *   [9 .. 95]  the values: quarter 0's in bit order, then quarter 1's, 2's and 3's.
+ *   A row with more than GCN_PACK384_CAPACITY values is OVERFLOWED: masks and header are valid, its value words are
+ *   undefined and a reader takes the dense row.  Words past 9 + total are undefined; no reader may depend on them.
+ * gcn_rows_pack384      : src [m, 256] fp32 (ld a multiple of 4, 16-byte aligned) -> slots [m][96].  One streaming
+ *   pass: reads 1 KiB and writes 384 bytes per row.
+ * gcn_spmm_csr_packed384: gcn_spmm_csr_packed on the slots of gcn_rows_pack384 — the same products in the same
+ *   order, bit-identical to gcn_spmm_csr on B.
+ */
+#define GCN_PACK384_CAPACITY 87
+int gcn_rows_pack384(const float *src, int64_t ld, int64_t m, uint32_t *slots, void *stream);
+int gcn_spmm_csr_packed384(const gcn_csr_plan *plan, const uint32_t *slots, const float *B, int64_t ldb, float *C,
+                           int64_t ldc, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * ReLU + training-mode BatchNorm over the rows of a contiguous row-major [n_rows, F] activation —
  * the fork's live model normalises the output of its first two layers,
  *     x = self.apply_bn(F.relu(self.gc1(x, adj)))                 reference pygcn/models.py:49,53

@@ -111,6 +111,8 @@ SIGNATURES = {
     "gcn_bits_row_counts": (i, [p, i64, i64, p, p]),
     "gcn_rows_pack512": (i, [p, i64, i64, p, p]),
     "gcn_spmm_csr_packed": (i, [plan_p, p, p, i64, p, i64, p, sz, p]),
+    "gcn_rows_pack384": (i, [p, i64, i64, p, p]),
+    "gcn_spmm_csr_packed384": (i, [plan_p, p, p, i64, p, i64, p, sz, p]),
     "gcn_bn_workspace_bytes": (sz, [i64, i64, i]),
     "gcn_bn_stats": (i, [i, p, i64, i64, i, f32, p, p, p, p, sz, p]),
     "gcn_bn_apply": (i, [i, p, p, i64, i64, i, p, p, p, p, p]),

@@ -240,6 +240,81 @@ __global__ __launch_bounds__(kWave *kRowsPerBlock) void pack512_kernel(const flo
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// POOLED 384-byte form (gcn_spmm_csr_packed384; the format: include/gcn_spmm.h): 96 words per row — the four masks
+// in words 0..7, the header in word 8 (running quarter counts in bytes 0..2, min(total, 255) in byte 3), ONE pool of
+// values from word 9 on, quarter after quarter.  pack512_kernel's structure: rows per wave with their 16-byte loads
+// first, the masks by DPP OR, a value at its rank in a wave-private LDS image, wavefront-scope fences only.  A
+// value's rank is where its quarter begins in the pool — the counts of the quarters before it, exchanged through
+// v_readlane of lanes 0, 16, 32 (wave-uniform) — plus its rank inside the quarter.  The image leaves as 384
+// contiguous bytes: 8 bytes per lane on lanes 0..47, three whole lines.  Ranks from 87 on are not written (the row
+// is overflowed: its value words are undefined), so nothing is written past word 95.
+constexpr int kPack384Cap = GCN_PACK384_CAPACITY;
+constexpr int kPack384Words = 96;
+static_assert(9 + kPack384Cap == kPack384Words, "masks + header + pool fill the slot");
+#ifndef GCN_PACK384_ROWS_PER_WAVE
+#define GCN_PACK384_ROWS_PER_WAVE 2
+#endif
+constexpr int kPack384RowsPerWave = GCN_PACK384_ROWS_PER_WAVE;
+constexpr int kPack384RowsPerBlock = kRowsPerBlock * kPack384RowsPerWave;
+
+__global__ __launch_bounds__(kWave *kRowsPerBlock) void pack384_kernel(const float *__restrict__ src, int64_t ld,
+                                                                       int64_t m, uint32_t *__restrict__ slots)
+{
+    constexpr int R = kPack384RowsPerWave;
+    __shared__ __attribute__((aligned(16))) uint32_t image_all[kRowsPerBlock * R * kPack384Words];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t r0 = ((int64_t)blockIdx.x * kRowsPerBlock + wave) * R;
+    if (r0 >= m) return;
+    const int nr = (int)(m - r0 < R ? m - r0 : R);           // wave-uniform
+    const int q = lane >> 4, i = lane & 15;
+    uint32_t *image = image_all + wave * (R * kPack384Words);
+    uint4 v[R];
+#pragma unroll
+    for (int k = 0; k < R; ++k)    // (rows past m: the last row again, loaded and not stored)
+        v[k] = *(const uint4 *)(src + (r0 + (k < nr ? k : nr - 1)) * ld + 16 * i + 4 * q);
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        const uint32_t x[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+        uint32_t nib = 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) nib |= (x[j] != 0u ? 1u : 0u) << j;
+        const uint32_t lo = or16(i < 8 ? nib << (4 * i) : 0u), hi = or16(i >= 8 ? nib << (4 * (i - 8)) : 0u);
+        const unsigned long long mask = ((unsigned long long)hi << 32) | lo;
+        const int cq = __builtin_popcountll(mask);
+        const uint32_t s1 = (uint32_t)__builtin_amdgcn_readlane(cq, 0);            // c0
+        const uint32_t s2 = s1 + (uint32_t)__builtin_amdgcn_readlane(cq, 16);      // c0 + c1
+        const uint32_t s3 = s2 + (uint32_t)__builtin_amdgcn_readlane(cq, 32);      // c0 + c1 + c2  (<= 192)
+        const uint32_t total = s3 + (uint32_t)__builtin_amdgcn_readlane(cq, 48);
+        const uint32_t header = s1 | (s2 << 8) | (s3 << 16) | ((total < 255u ? total : 255u) << 24);
+        int rank = (int)(q == 0 ? 0u : q == 1 ? s1 : q == 2 ? s2 : s3)
+                   + __builtin_popcountll(mask & ((1ull << (4 * i)) - 1ull));
+        uint32_t *img = image + k * kPack384Words;
+        if (i < 2) img[2 * q + i] = i == 0 ? lo : hi;
+        if (lane == 2) img[8] = header;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if ((nib >> j) & 1u) {
+                if (rank < kPack384Cap) img[9 + rank] = x[j];
+                ++rank;
+            }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane < kPack384Words / 2) {
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            if (k < nr) {
+                const uint2 w = *(const uint2 *)(image + k * kPack384Words + 2 * lane);
+                *(uint2 *)(slots + (r0 + k) * kPack384Words + 2 * lane) = w;
+            }
+        }
+    }
+}
+
 int check(const char *who, int dtype, int64_t m, int64_t F, int64_t ld)
 {
     if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16) return gcn_internal_fail(GCN_E_BADARG, who);
@@ -320,6 +395,20 @@ int gcn_rows_pack512(const float *src, int64_t ld, int64_t m, uint32_t *slots, v
     const dim3 grid((unsigned)blocks), block(kWave * kRowsPerBlock);
     hipLaunchKernelGGL(pack512_kernel, grid, block, 0, (hipStream_t)stream, src, ld, m, slots);
     return launched("gcn_rows_pack512 launch");
+}
+
+int gcn_rows_pack384(const float *src, int64_t ld, int64_t m, uint32_t *slots, void *stream)
+{
+    if (m < 0 || ld < 256 || ld % 4 != 0) return gcn_internal_fail(GCN_E_BADARG, "gcn_rows_pack384: bad sizes (256 columns, ld a multiple of 4)");
+    if (m == 0) return 0;
+    if (src == nullptr || slots == nullptr) return gcn_internal_fail(GCN_E_BADARG, "gcn_rows_pack384: NULL pointer");
+    if ((((uintptr_t)src) | ((uintptr_t)slots)) % 16 != 0)
+        return gcn_internal_fail(GCN_E_ALIGN, "gcn_rows_pack384: 16-byte alignment required");
+    const int64_t blocks = (m + kPack384RowsPerBlock - 1) / kPack384RowsPerBlock;
+    if (blocks > INT32_MAX) return gcn_internal_fail(GCN_E_BADARG, "gcn_rows_pack384: too many rows");
+    const dim3 grid((unsigned)blocks), block(kWave * kRowsPerBlock);
+    hipLaunchKernelGGL(pack384_kernel, grid, block, 0, (hipStream_t)stream, src, ld, m, slots);
+    return launched("gcn_rows_pack384 launch");
 }
 
 int gcn_bits_row_counts(const uint32_t *bits, int64_t m, int64_t words, int32_t *counts, void *stream)

@@ -90,7 +90,7 @@ struct KParams {
     const uint32_t *csel;       // optional bitmap over output rows: clear bit = row not wanted
     int32_t cskip;              // with cflag: all-zero rows are not stored
     uint32_t *cabsmax;          // optional output: max |stored value| as BITS (atomic max; inf / NaN sort on top)
-    const void *packed;         // spmm_wide_packed_kernel: the 512-byte slots of the rows of B (gcn_rows_pack512)
+    const void *packed;         // spmm_wide_packed_kernel: the slots of the rows of B (gcn_rows_pack512 / _pack384)
 };
 
 // ------------------------------------------------------------------------------------------
@@ -513,6 +513,9 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void spmm_wide_kernel(KParam
 //     fmaf(a, 0, acc) as the dense zero does — so the result is bit-identical;
 //   * an entry whose slot reports an overflowed quarter (count > 29; wave-uniform test on the loaded words)
 //     takes its four values from the dense row instead, in place: the order of the sum does not change.
+//   * the POOLED 384-byte slots of gcn_rows_pack384 (gcn_spmm_csr_packed384) go through the same code with another
+//     slot geometry (SlotGeom below): three lines per entry instead of four, one pool of values, the lane's first
+//     word 9 + prefix(q) + popcount(mask below bit 4i).  The nibble queue and the fmaf order are the same;
 // Row bookkeeping, long-row chunks (fp32 partial slab, spmm_long_reduce_kernel) and the store are wide_stream's;
 // only the column a lane owns differs (the store is still 16 bytes per lane, one full row per wave).
 // ------------------------------------------------------------------------------------------
@@ -527,15 +530,42 @@ __device__ __forceinline__ u32x2 slot_load8(uint64_t base, uint32_t nbytes, uint
     return __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, 0, 0);
 }
 
-constexpr int kPackSlotBytes = 512;
-constexpr uint32_t kPackCap = GCN_PACK512_CAPACITY;
-// LDS image of one staged slot, in words: sub-slots at 0, 48, 84, 132, 36 words each (see above)
-constexpr int kStageWords = 168;
-// An OVERFLOWED quarter (its values come from the dense row) may have all 64 bits set: its lanes' discarded
-// reads reach word 3 + 60 + 3 of the sub-slot, 31 words past the copy — into the wave's next copy, the next
-// wave's, or this tail behind the last wave's.
-constexpr int kStageTailWords = 32;
-template <int D> constexpr int stage_block_words() { return kWavesPerBlock * D * kStageWords + kStageTailWords; }
+// THE SLOT GEOMETRY: all that differs between the two fixed-slot formats (include/gcn_spmm.h), as the compile-time
+// parameter of packed_stream and spmm_wide_packed_kernel.  Lane (q, i) = (lane >> 4, lane & 15) throughout.
+//   kBytes       a slot in memory; the load is 8 bytes per lane at 8 * lane, lanes from kLanes on are past
+//                num_records and read zeros without traffic
+//   kStageWords  the LDS image of one staged slot; own_word: where a lane stages its 8 bytes; mask_word: the
+//                quarter's 64-bit mask; pool_word: word 0 of the values the lane's ranks count from
+//   kTailWords   behind the last wave's last copy: how far a DISCARDED read may reach past a copy (below)
+template <int BYTES> struct SlotGeom;
+// 512: four sub-slots (mask, count, 29 values).  Image: sub-slots at 0, 48, 84, 132, 36 words each (see above).  An
+// OVERFLOWED quarter (its values come from the dense row) may have all 64 bits set: its lanes' discarded reads reach
+// word 3 + 60 + 3 of the sub-slot, 31 words past the copy — into the wave's next copy, the next wave's, or the tail.
+template <> struct SlotGeom<512> {
+    static constexpr int kBytes = 512, kLanes = 64, kStageWords = 168, kTailWords = 32;
+    static constexpr uint32_t kCap = GCN_PACK512_CAPACITY;
+    static constexpr bool kPooled = false;
+    static __device__ __forceinline__ int mask_word(int q) { return 42 * q + 6 * (q & 1); }
+    static __device__ __forceinline__ int own_word(int q, int i) { return mask_word(q) + 2 * i; }
+    static __device__ __forceinline__ int pool_word(int q) { return mask_word(q) + 3; }
+};
+// 384: masks in words 0..7, header in word 8, ONE pool of 87 values from word 9.  The image is the slot as it is in
+// words 0..95; the copy is SIZED at 128 words so that lanes 48..63, which hold zeros, stage them in words 96..127 of
+// their own copy and the ds_write_b64 needs no mask (a masked write compiled to a branch per staged slot).  The place
+// of a lane's first value is 9 + prefix(q) + popcount(mask_q below bit 4 i), prefix(q) = byte q - 1 of the header (0
+// for q = 0).  The two quarters of a 32-lane half read consecutive runs of the pool, so the 512 form's bank offset
+// has no counterpart.  Discarded reads: a row that fits reads up to word 9 + 87 + 2 = 98; an OVERFLOWED row with
+// all 256 bits set computes 9 + 252 and reads up to word 264 — 137 words past its copy.  The tail is SIZED for that
+// (no clamp: a clamp is one more VALU per entry), and whatever is read there is selected away bit by bit (expand).
+template <> struct SlotGeom<384> {
+    static constexpr int kBytes = 384, kLanes = 48, kStageWords = 128, kTailWords = 9 + 252 + 4 - 128;
+    static constexpr uint32_t kCap = GCN_PACK384_CAPACITY;
+    static constexpr bool kPooled = true;
+    static __device__ __forceinline__ int mask_word(int q) { return 2 * q; }
+    static __device__ __forceinline__ int own_word(int q, int i) { return 2 * (16 * q + i); }
+    static __device__ __forceinline__ int pool_word(int) { return 9; }
+};
+template <typename G, int D> constexpr int stage_block_words() { return kWavesPerBlock * D * G::kStageWords + G::kTailWords; }
 
 // Orders this wave's LDS writes and reads of its own copies (no other wave touches them): compiler fences of
 // wavefront scope, no instruction and no workgroup barrier.
@@ -546,7 +576,7 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int D, bool ROWS>
+template <typename G, int D, bool ROWS>
 __device__ __forceinline__ void packed_stream(const KParams &p, uint32_t *stage, const int32_t *__restrict__ colp,
                                               const float *__restrict__ valp, int ne, int lane, float (&acc)[4],
                                               int rel_end, int nr, int64_t row0, int f, const float (&bias)[4])
@@ -556,12 +586,16 @@ __device__ __forceinline__ void packed_stream(const KParams &p, uint32_t *stage,
     const uint32_t voff = (uint32_t)lane * 8u;
     // lane-static: this lane's sub-slot in a staged copy and its own two words there; which mask word holds its
     // nibble and where; the bits below its nibble in either mask word
-    uint32_t *const sub = stage + 42 * q + 6 * (q & 1);
-    uint32_t *const mine = sub + 2 * i;
+    uint32_t *const sub = stage + G::mask_word(q);        // the quarter's mask in a staged copy
+    uint32_t *const mine = stage + G::own_word(q, i);
+    uint32_t *const pool = stage + G::pool_word(q);       // word 0 of the values the lane's ranks count from
     const bool upper = i >= 8;
     const uint32_t sh = 4u * (uint32_t)(i & 7);
     const uint32_t below_lo = upper ? ~0u : (1u << sh) - 1u, below_hi = upper ? (1u << sh) - 1u : 0u;
-    const bool cnt_lane = i == 1;                         // loads words 2, 3 of its sub-slot: .x is the count
+    const bool cnt_lane = i == 1;                         // (512) loads words 2, 3 of its sub-slot: .x is the count
+    // (384) where the lane's quarter begins in the pool: bits [pre_off, pre_off + pre_len) of the header word —
+    // byte q - 1, and no bits at all (v_bfe_u32 of width 0 = 0) for quarter 0
+    const uint32_t pre_off = q > 0 ? 8u * (uint32_t)(q - 1) : 0u, pre_len = q > 0 ? 8u : 0u;
     int r = 0;
     int rend = ROWS ? readlane_i(rel_end, 0) : INT_MAX;
     // store row rr of the item and start the next one
@@ -626,19 +660,24 @@ __device__ __forceinline__ void packed_stream(const KParams &p, uint32_t *stage,
             for (int j = 0; j < D; ++j) {
                 const bool ok = k + j < cnt;
                 cc[j] = readlane_i(cv, k + j);   // k + j <= 63 always (k <= 56)
-                x[j] = slot_load8((uint64_t)p.packed + (uint64_t)(uint32_t)cc[j] * (uint64_t)kPackSlotBytes,
-                                  ok ? (uint32_t)kPackSlotBytes : 0u, voff);
+                x[j] = slot_load8((uint64_t)p.packed + (uint64_t)(uint32_t)cc[j] * (uint64_t)G::kBytes,
+                                  ok ? (uint32_t)G::kBytes : 0u, voff);
             }
-            // stage the D slots (the previous group's reads come first); one test per group tells whether any of
-            // them overflowed (the largest count word: .x of lane 1 of a quarter)
+            // stage the D slots (the previous group's reads come first).  512: one test per group tells whether any of
+            // them overflowed (the largest count word: .x of lane 1 of a quarter).  384: the header word is .x of lane
+            // 4; v_readlane makes it wave-uniform, so "overflowed" is one scalar compare per entry (byte 3 is the
+            // total: total > 87 <=> header >= 88 << 24) with no ballot and no test per group, and the prefixes below
+            // are cut from the same scalar register
             wave_sync();
-            uint32_t top = 0u;
+            uint32_t top = 0u, hdr[D];
 #pragma unroll
             for (int j = 0; j < D; ++j) {
-                *(u32x2 *)(mine + j * kStageWords) = x[j];
-                top = max(top, x[j].x);
+                *(u32x2 *)(mine + j * G::kStageWords) = x[j];
+                if constexpr (G::kPooled) hdr[j] = (uint32_t)__builtin_amdgcn_readlane((int)x[j].x, 4);
+                else top = max(top, x[j].x);
             }
-            const bool any_over = __ballot(cnt_lane && top > kPackCap) != 0ull;
+            bool any_over = true;
+            if constexpr (!G::kPooled) any_over = __ballot(cnt_lane && top > G::kCap) != 0ull;
             wave_sync();
             // kMaskGroup masks at a time -> per entry the lane's nibble and the place of its first value; then,
             // kValueGroup entries at a time, the value words and the arithmetic.  (The group sizes are what 72
@@ -652,13 +691,22 @@ __device__ __forceinline__ void packed_stream(const KParams &p, uint32_t *stage,
                 u32x2 h[kMaskGroup];
                 wave_sync();        // (keeps these reads behind the previous group's arithmetic)
 #pragma unroll
-                for (int j = 0; j < kMaskGroup; ++j) h[j] = *(const u32x2 *)(sub + (g0 + j) * kStageWords);
+                for (int j = 0; j < kMaskGroup; ++j) h[j] = *(const u32x2 *)(sub + (g0 + j) * G::kStageWords);
 #pragma unroll
                 for (int j = 0; j < kMaskGroup; ++j) {
                     nibs[j] = (upper ? h[j].y : h[j].x) >> sh;
-                    int w0 = __builtin_popcount(h[j].x & below_lo) + __builtin_popcount(h[j].y & below_hi);
+                    int w0;
+                    if constexpr (G::kPooled) {      // (the prefix rides in the first v_bcnt's addend, the first sum
+                        w0 = (int)__builtin_amdgcn_ubfe(hdr[g0 + j], pre_off, pre_len);     //  in the second's)
+                        asm("" : "+v"(w0));
+                        w0 += __builtin_popcount(h[j].x & below_lo);
+                        asm("" : "+v"(w0));
+                        w0 += __builtin_popcount(h[j].y & below_hi);
+                    } else {
+                        w0 = __builtin_popcount(h[j].x & below_lo) + __builtin_popcount(h[j].y & below_hi);
+                    }
                     asm("" : "+v"(w0));      // (keeps the sum in v_bcnt's addend: the scaling by 4 comes after)
-                    first[j] = sub + (g0 + j) * kStageWords + 3 + w0;        // (over: see kStageTailWords)
+                    first[j] = pool + (g0 + j) * G::kStageWords + w0;        // (over: see SlotGeom::kTailWords)
                 }
 #pragma unroll
                 for (int g = 0; g < kMaskGroup; g += kValueGroup) {
@@ -674,9 +722,10 @@ __device__ __forceinline__ void packed_stream(const KParams &p, uint32_t *stage,
 #pragma unroll
                     for (int j = 0; j < kValueGroup; ++j) {
                         const int e = g0 + g + j;                            // the entry's place among the D
-                        consume(min(t + k + e, ne - 1), xs[j],
-                                any_over && __ballot(sub[e * kStageWords + 2] > kPackCap) != 0ull,
-                                readlane_f(vv, k + e), cc[e]);
+                        bool over;
+                        if constexpr (G::kPooled) over = hdr[e] >= ((G::kCap + 1u) << 24);
+                        else over = any_over && __ballot(sub[e * G::kStageWords + 2] > G::kCap) != 0ull;
+                        consume(min(t + k + e, ne - 1), xs[j], over, readlane_f(vv, k + e), cc[e]);
                     }
                 }
             }
@@ -690,7 +739,7 @@ __device__ __forceinline__ void packed_stream(const KParams &p, uint32_t *stage,
     }
 }
 
-template <typename IdxT, int D>
+template <typename IdxT, int D, int SLOT>
 __global__ __launch_bounds__(kWave *kWavesPerBlock) __attribute__((amdgpu_waves_per_eu(7, 8)))
 void spmm_wide_packed_kernel(KParams p)
 {
@@ -702,15 +751,16 @@ void spmm_wide_packed_kernel(KParams p)
     const IdxT *__restrict__ rp = (const IdxT *)p.rowptr;
     float acc[4] = {0.f, 0.f, 0.f, 0.f}, bias[4] = {0.f, 0.f, 0.f, 0.f};
     // D staged slot copies per wave, private to it (packed_stream; no __syncthreads anywhere below)
-    __shared__ __attribute__((aligned(16))) uint32_t stage_all[stage_block_words<D>()];
-    uint32_t *stage = stage_all + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * (D * kStageWords);
+    typedef SlotGeom<SLOT> G;
+    __shared__ __attribute__((aligned(16))) uint32_t stage_all[stage_block_words<G, D>()];
+    uint32_t *stage = stage_all + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * (D * G::kStageWords);
 
     if (item < p.n_chunks) {
         // ---- one chunk of a long row -> fp32 partial slab
         const int row = p.chunk_row[item];
         const int64_t e0 = p.chunk_e0[item];
         const int64_t e1 = min(e0 + (int64_t)p.long_thresh, (int64_t)rp[row + 1]);
-        packed_stream<D, false>(p, stage, p.col + e0, p.val + e0, (int)(e1 - e0), lane, acc, 0, 0, 0, f, bias);
+        packed_stream<G, D, false>(p, stage, p.col + e0, p.val + e0, (int)(e1 - e0), lane, acc, 0, 0, 0, f, bias);
         float *dst = p.partial + (int64_t)item * p.F + f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) dst[k] = acc[k];
@@ -727,7 +777,7 @@ void spmm_wide_packed_kernel(KParams p)
 #pragma unroll
         for (int k = 0; k < 4; ++k) bias[k] = p.bias[f + k];
     }
-    packed_stream<D, true>(p, stage, p.col + ea, p.val + ea, ne, lane, acc, rel_end, nr, (int64_t)ra, f, bias);
+    packed_stream<G, D, true>(p, stage, p.col + ea, p.val + ea, ne, lane, acc, rel_end, nr, (int64_t)ra, f, bias);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1339,7 +1389,7 @@ int next_pow2(int v)
 }
 
 template <typename T, int VECW>
-int spmm_typed(const gcn_csr_plan *plan, KParams &kp, hipStream_t s)
+int spmm_typed(const gcn_csr_plan *plan, KParams &kp, hipStream_t s, int slot_bytes)
 {
     const int F = kp.F;
     const bool is64 = plan->rowptr_is64 != 0;
@@ -1359,8 +1409,11 @@ int spmm_typed(const gcn_csr_plan *plan, KParams &kp, hipStream_t s)
         if (kp.packed != nullptr) {
             if constexpr (sizeof(T) == 4) {      // (fp32, F = 256, aligned: gcn_spmm_csr_packed checked)
                 const dim3 grid(nblk, 1), block(kWave * kWavesPerBlock);
-                pick_index(is64, [&](auto i) {
-                    hipLaunchKernelGGL((spmm_wide_packed_kernel<typename decltype(i)::type, 8>), grid, block, 0, s, kp);
+                pick_int<512, 384>(slot_bytes, [&](auto g) {
+                    pick_index(is64, [&](auto i) {
+                        hipLaunchKernelGGL((spmm_wide_packed_kernel<typename decltype(i)::type, 8, decltype(g)::value>),
+                                           grid, block, 0, s, kp);
+                    });
                 });
             }
         } else if (vec_ok) {
@@ -1590,7 +1643,7 @@ size_t gcn_spmm_workspace_bytes(const gcn_csr_plan *plan, int64_t F)
 // gcn_spmm_csr_ep, and (`packed` != NULL: the slots of the rows of B) gcn_spmm_csr_packed
 static int spmm_csr_impl(const gcn_csr_plan *plan, int dtype, const void *B, int64_t ldb, void *C,
                          int64_t ldc, int64_t F, const gcn_epilogue *ep, void *workspace,
-                         size_t workspace_bytes, void *stream, const void *packed)
+                         size_t workspace_bytes, void *stream, const void *packed, int slot_bytes = 512)
 {
     const float *bias = ep ? ep->bias : nullptr;
     const int relu = ep ? ep->relu : 0;
@@ -1668,7 +1721,7 @@ static int spmm_csr_impl(const gcn_csr_plan *plan, int dtype, const void *B, int
     hipStream_t s = (hipStream_t)stream;
     return pick_dtype(dtype, [&](auto t) {
         typedef typename decltype(t)::type T;
-        return spmm_typed<T, Lane<T>::V>(plan, kp, s);
+        return spmm_typed<T, Lane<T>::V>(plan, kp, s, slot_bytes);
     });
 }
 
@@ -1686,6 +1739,16 @@ int gcn_spmm_csr_packed(const gcn_csr_plan *plan, const uint32_t *slots, const f
     if ((((uintptr_t)slots) | ((uintptr_t)B) | ((uintptr_t)C)) % 16 != 0 || ldb % 4 != 0 || ldc % 4 != 0)
         return fail(GCN_E_ALIGN, "gcn_spmm_csr_packed: 16-byte aligned slots and rows required");
     return spmm_csr_impl(plan, GCN_DTYPE_F32, B, ldb, C, ldc, 256, nullptr, workspace, workspace_bytes, stream, slots);
+}
+
+int gcn_spmm_csr_packed384(const gcn_csr_plan *plan, const uint32_t *slots, const float *B, int64_t ldb, float *C,
+                           int64_t ldc, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (slots == nullptr || B == nullptr) return fail(GCN_E_BADARG, "gcn_spmm_csr_packed384: slots or B is NULL");
+    if ((((uintptr_t)slots) | ((uintptr_t)B) | ((uintptr_t)C)) % 16 != 0 || ldb % 4 != 0 || ldc % 4 != 0)
+        return fail(GCN_E_ALIGN, "gcn_spmm_csr_packed384: 16-byte aligned slots and rows required");
+    return spmm_csr_impl(plan, GCN_DTYPE_F32, B, ldb, C, ldc, 256, nullptr, workspace, workspace_bytes, stream, slots,
+                         384);
 }
 
 int gcn_spmm_csr(const gcn_csr_plan *plan, int dtype, const void *B, int64_t ldb, void *C,

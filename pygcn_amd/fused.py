@@ -220,8 +220,8 @@ _PACKED_HIDDEN = os.environ.get("PYGCN_PACKED_HIDDEN", "1") != "0"
 def set_packed_hidden(enabled):
     """Layer 2 of the training-mode forward pass as (Â·h1)·W2 over PACKED hidden rows:
 
-        P    = rows_pack512(h1)                     512-byte slots: masks + the non-zero values (>= 75 % of h1 is 0)
-        z2   = Â·P                                  the wide SpMM gathering half the bytes per stored entry
+        P    = rows_pack384(h1)                     384-byte slots: masks + the non-zero values (>= 75 % of h1 is 0)
+        z2   = Â·P                                  the wide SpMM gathering 3/8 of the bytes per stored entry
         logp = log_softmax(z2·W2 + b2)              the contiguous-row GEMM with the log_softmax epilogue
 
     instead of log_softmax(Â·(h1·W2) + b2).  Taken where packed_hidden_applies(); every other call, eval mode
@@ -246,7 +246,7 @@ def packed_hidden_applies(h1, w2, b2, dropout_p):
 
 def _layer2_packed(graph, h1, w2, b2):
     """logp by the packed route, or None where the log_softmax GEMM declines the operands."""
-    z2 = spmm_csr(graph, packed=_spmm.rows_pack512(h1))
+    z2 = spmm_csr(graph, packed=_spmm.rows_pack384(h1))
     return _gemm.gemm_xw256_log_softmax(z2, w2, b2)
 
 

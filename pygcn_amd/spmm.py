@@ -45,16 +45,23 @@ def set_timing_records(records):
 
 
 class PackedRows:
-    """A 256-wide fp32 matrix as fixed 512-byte slots (rows_pack512) next to the matrix itself: `slots` int32
-    [m, 128] — per row four 128-byte sub-slots, one per column quarter (64-bit mask, count, non-zero values in
-    bit order; include/gcn_spmm.h) — and `dense`, read by a gather only for rows a quarter of which did not fit."""
-    __slots__ = ("slots", "dense")
+    """A 256-wide fp32 matrix as fixed slots next to the matrix itself: `slots` int32 [m, slot_bytes / 4], `dense`,
+    read by a gather only for the rows that did not fit their slot, and `slot_bytes`, the format (include/gcn_spmm.h):
+    512 (rows_pack512) — per row four 128-byte sub-slots, one per column quarter (64-bit mask, count, 29 values in
+    bit order); 384 (rows_pack384) — the four masks, a header of running quarter counts and ONE pool of 87 values.
+    Without `slot_bytes` the format is read off the width of `slots`."""
+    __slots__ = ("slots", "dense", "slot_bytes")
 
-    def __init__(self, slots, dense):
+    def __init__(self, slots, dense, slot_bytes=None):
         self.slots, self.dense = slots, dense
+        self.slot_bytes = 4 * slots.shape[1] if slot_bytes is None else int(slot_bytes)
+        if self.slot_bytes not in _PACKED_ENTRY:
+            raise RuntimeError(f"PackedRows: no slot format of {self.slot_bytes} bytes (512 or 384)")
 
 
 PACK512_CAPACITY = 29      # values per sub-slot (GCN_PACK512_CAPACITY)
+PACK384_CAPACITY = 87      # values per slot (GCN_PACK384_CAPACITY)
+_PACKED_ENTRY = {512: "gcn_spmm_csr_packed", 384: "gcn_spmm_csr_packed384"}     # slot bytes -> the gather's entry point
 
 
 def rows_pack512_usable(h):
@@ -73,17 +80,30 @@ def rows_pack512(h):
     slots = torch.empty((h.shape[0], 128), dtype=torch.int32, device=h.device)
     if h.shape[0]:
         _native.launch("gcn_rows_pack512", h.device, h.data_ptr(), h.stride(0), h.shape[0], slots.data_ptr())
-    return PackedRows(slots, h)
+    return PackedRows(slots, h, 512)
+
+
+def rows_pack384(h):
+    """PackedRows of `h` in the pooled 384-byte format (C-ABI gcn_rows_pack384: one streaming pass, 1 KiB read and
+    384 bytes written per row): three 128-byte lines per gathered row instead of four.  Takes what rows_pack512
+    takes (rows_pack512_usable)."""
+    _require_cuda(h, "h")
+    if not rows_pack512_usable(h):
+        raise RuntimeError(f"rows_pack384: {tuple(h.shape)} {h.dtype}: fp32 [m, 256] with 16-byte aligned rows")
+    slots = torch.empty((h.shape[0], 96), dtype=torch.int32, device=h.device)
+    if h.shape[0]:
+        _native.launch("gcn_rows_pack384", h.device, h.data_ptr(), h.stride(0), h.shape[0], slots.data_ptr())
+    return PackedRows(slots, h, 384)
 
 
 def _spmm_csr_packed(graph, packed, out, tag):
-    """spmm_csr's launch for a PackedRows operand (C-ABI gcn_spmm_csr_packed): plain product, bit-identical to
-    the dense launch on packed.dense."""
+    """spmm_csr's launch for a PackedRows operand (C-ABI gcn_spmm_csr_packed / gcn_spmm_csr_packed384 by the
+    operand's format): plain product, bit-identical to the dense launch on packed.dense."""
     if not isinstance(graph, CSRGraph) or not isinstance(packed, PackedRows):
         raise RuntimeError("spmm_csr: graph must be a CSRGraph and packed a PackedRows")
     B, slots = packed.dense, packed.slots
     if B.shape[0] != graph.shape[1] or B.device != graph.device or not rows_pack512_usable(B) \
-            or tuple(slots.shape) != (B.shape[0], 128) or not slots.is_contiguous():
+            or tuple(slots.shape) != (B.shape[0], packed.slot_bytes // 4) or not slots.is_contiguous():
         raise RuntimeError(f"size mismatch, adj {graph.shape} x packed {tuple(B.shape)}")
     n_rows = graph.shape[0]
     if out is None:
@@ -101,7 +121,7 @@ def _spmm_csr_packed(graph, packed, out, tag):
         if rec is not None:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-        _native.launch("gcn_spmm_csr_packed", B.device, plan, slots.data_ptr(), B.data_ptr(), B.stride(0),
+        _native.launch(_PACKED_ENTRY[packed.slot_bytes], B.device, plan, slots.data_ptr(), B.data_ptr(), B.stride(0),
                        out.data_ptr(), out.stride(0), ws.data_ptr() if ws is not None else None, ws_bytes)
         if rec is not None:
             ev1.record()
@@ -134,7 +154,7 @@ def spmm_csr(graph, B=None, bias=None, relu=False, out=None, tag="fwd", dropout_
     `c_absmax`: optional DEVICE float32 [1], zeroed by the caller: receives max|stored value| of the
     launch (gcn_epilogue.c_absmax) — the bound a scaled GEMM consuming the result needs, without a
     reduction pass; non-finite if the result holds inf / NaN.
-    `packed` (a PackedRows, INSTEAD of B): the operand's rows are gathered from their 512-byte slots — the same
+    `packed` (a PackedRows, INSTEAD of B): the operand's rows are gathered from their 512- or 384-byte slots — the same
     products in the same order, bit-identical to the launch on packed.dense; plain product only."""
     if packed is not None:
         if (B is not None or bias is not None or relu or dropout_p or b_hint is not None or B2 is not None
