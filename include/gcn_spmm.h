@@ -1046,6 +1046,45 @@ int gcn_agg_linear_backward(const float *g, const float *y, const float *z, int6
                             int64_t Fout, int64_t batch, int relu, float *grad_w, float *grad_b, double *partials,
                             int64_t partial_rows, void *stream);
 
+/*
+ * Dense adjacency ingest (pygcn_amd/csrc/gcn_dense.hip): a dense fp32 matrix A [n_rows, n_cols], row pitch lda >=
+ * n_cols elements, to CSR — the fork loads its co-visit matrix as a dense [N, N] float tensor (reference
+ * pygcn/utils.py:124-131) and never builds a sparse one.  Two sweeps with the caller's scan between them, as
+ * gcn_csr_take_rows has it.  All pointers DEVICE; nothing is read by the host.  Row i, entries a_j = A[i * lda + j]:
+ *   THE VALUE RULE   GCN_DENSE_NONZERO   keep a  iff  !(a == 0):  -0 and +0 dropped, NaN kept (torch.nonzero's rule);
+ *                    GCN_DENSE_GREATER   keep a  iff  a > bound, the ordinary float comparison: NaN dropped.
+ *   thr == NULL      entry j is kept iff the value rule holds.
+ *   thr != NULL      count_gt must be non-NULL and 1 <= keep <= n_cols.  thr[i] and count_gt[i] are gcn_select_kth's
+ *                    answers for window i at kth = keep (A contiguous is exactly its [batch = n_rows, n_rows = n_cols]
+ *                    layout).  The selected set S_i is every entry whose key is greater than thr[i], plus the
+ *                    lowest-column entries whose key equals it, until S_i has `keep` members; keys compare in the
+ *                    selection ORDER above (-0 is +0, every NaN above +inf).  Entry j is kept iff j is in S_i AND the
+ *                    value rule holds: a row keeps at most `keep` entries, and a row with fewer non-zeros than `keep`
+ *                    keeps just those.
+ *   gcn_dense_to_csr_count   row_count[i] (int32 [n_rows]) = the number of kept entries of row i.
+ *   gcn_dense_to_csr_fill    writes the kept entries of row i at rowptr[i] + 0, 1, ... in ASCENDING COLUMN ORDER:
+ *                            col int32, val the stored float bit for bit (a NaN keeps its payload, nothing is
+ *                            canonicalised).  rowptr [n_rows + 1] is the caller's exclusive scan of row_count (int32,
+ *                            or int64 with rowptr_is64).  Nothing outside [0, rowptr[n_rows]) is written, and nothing
+ *                            outside row i's slots for row i, whatever rowptr says.
+ * One 256-thread block per row, rows grid-stride from a grid of at most GCN_DENSE_SWEEP_ROWS blocks, so any n_rows
+ * below 2^31 runs; a row is read in chunks of 1024 columns, four per lane as one 16-byte access where A + i * lda is
+ * 16-byte aligned, else element by element; the fill ranks a chunk's kept entries by ballots and popcounts (one
+ * barrier per chunk).  A matrix of few very long rows under-fills the chip.  No atomics: two runs give the same bytes.
+ * GCN_E_BADARG: n_rows < 0, n_cols < 1 or n_cols >= 2^31, lda < n_cols, an unknown rule, thr without count_gt, keep
+ * outside [1, n_cols] with thr, a NULL array with n_rows > 0.  GCN_E_ALIGN: a pointer that is not 4-byte aligned (an
+ * int64 rowptr: 8-byte).  Checked before any launch; n_rows = 0 launches nothing and returns 0.
+ * (ABI 26, additive.)
+ */
+#define GCN_DENSE_NONZERO 0
+#define GCN_DENSE_GREATER 1
+#define GCN_DENSE_SWEEP_ROWS 8192   /* rows that one sweep of the grid covers */
+int gcn_dense_to_csr_count(const float *A, int64_t lda, int64_t n_rows, int64_t n_cols, int rule, float bound,
+                           const float *thr, const int32_t *count_gt, int64_t keep, int32_t *row_count, void *stream);
+int gcn_dense_to_csr_fill(const float *A, int64_t lda, int64_t n_rows, int64_t n_cols, int rule, float bound,
+                          const float *thr, const int32_t *count_gt, int64_t keep, const void *rowptr, int rowptr_is64,
+                          int32_t *col, float *val, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,9 @@ GCN_DEFAULT_ITEM_COST = 64
 GCN_DEFAULT_LONG_THRESH = 256
 GCN_DTYPE_F32 = 0
 GCN_DTYPE_BF16 = 1
+GCN_DENSE_NONZERO = 0
+GCN_DENSE_GREATER = 1
+GCN_DENSE_SWEEP_ROWS = 8192
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 c_i64p = ctypes.POINTER(ctypes.c_int64)
@@ -155,6 +158,8 @@ SIGNATURES = {
     "gcn_agg_linear_partial_rows": (i64, [i64, i64, i64, i64]),
     "gcn_agg_linear_forward": (i, [p, p, p, p, i64, i64, i64, i64, i, p]),
     "gcn_agg_linear_backward": (i, [p, p, p, i64, i64, i64, i64, i, p, p, p, i64, p]),
+    "gcn_dense_to_csr_count": (i, [p, i64, i64, i64, i, f32, p, p, i64, p, p]),
+    "gcn_dense_to_csr_fill": (i, [p, i64, i64, i64, i, f32, p, p, i64, p, i, p, p, p]),
 }
 EXPORTS = tuple(SIGNATURES)
 

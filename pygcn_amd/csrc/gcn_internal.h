@@ -225,6 +225,24 @@ __device__ __forceinline__ float act(float z, int relu) { return (relu && z < 0.
 // an integer and the fp32 evaluation is within 2^-22 * a / D of it — the truncation is exact
 __device__ __forceinline__ int fdiv(int a, float r) { return (int)(((float)a + 0.5f) * r); }
 
+// THE SELECTION ORDER on fp32 (include/gcn_spmm.h, "Vertex selection"; gcn_select, gcn_dense): -0 is +0, every NaN is
+// above +inf, otherwise numeric.  order_key() is the uint32 with that order: negatives have all bits flipped,
+// non-negatives the sign bit set, NaN is 0xFFFFFFFF.
+__device__ __forceinline__ uint32_t order_key(float f)
+{
+    uint32_t u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;       // NaN, any sign or payload
+    if (u == 0x80000000u) u = 0u;                                  // -0 is +0
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// the canonical float of a key: NaN is 0x7FC00000, zero is +0
+__device__ __forceinline__ float key_float(uint32_t t)
+{
+    if (t == 0xffffffffu) return __uint_as_float(0x7fc00000u);
+    return __uint_as_float((t & 0x80000000u) ? (t & 0x7fffffffu) : ~t);
+}
+
 // One DPP row operation CTRL on a register: a VALU modifier, no trip through the LDS crossbar and no address
 // registers.  quad_perm [1,0,3,2] = 0xB1 and [2,3,0,1] = 0x4E are the xor-1 / xor-2 exchanges; after them a quad
 // is uniform, so row_half_mirror = 0x141 (lane i <-> 7 - i) and row_mirror = 0x140 (i <-> 15 - i) act as

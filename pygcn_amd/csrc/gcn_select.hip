@@ -56,21 +56,6 @@ constexpr int64_t kBlocks = 1024;         // slabs of rows per window
 constexpr int64_t kRowsPerBlock = 1024;   // a block's slab is at least this long before a second block starts
 constexpr int64_t kMaxRows = INT32_MAX;   // n_rows < 2^31: counts and ranks are int32
 
-__device__ __forceinline__ uint32_t order_key(float f)
-{
-    uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;       // NaN, any sign or payload
-    if (u == 0x80000000u) u = 0u;                                  // -0 is +0
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// the canonical float of a key: NaN is 0x7FC00000, zero is +0
-__device__ __forceinline__ float key_float(uint32_t t)
-{
-    if (t == 0xffffffffu) return __uint_as_float(0x7fc00000u);
-    return __uint_as_float((t & 0x80000000u) ? (t & 0x7fffffffu) : ~t);
-}
-
 __host__ __device__ constexpr int pass_shift(int pass) { return pass == 0 ? 21 : (pass == 1 ? 10 : 0); }
 __host__ __device__ constexpr int pass_bins(int pass) { return pass == 2 ? 1024 : 2048; }
 // the bits the earlier passes fixed

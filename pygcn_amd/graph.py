@@ -185,16 +185,111 @@ class CSRGraph:
             g.share_transpose()
         return g
 
+    @classmethod
+    def from_dense(cls, adj, greater_than=None, keep_per_row=None, symmetrize=False, normalize=False,
+                   share_transpose=False, device=None, _rowptr_is64=None, **kw):
+        """A dense [n_rows, n_cols] adjacency — what the fork's live scripts hold (reference pygcn/utils.py:124-131,
+        `torch.FloatTensor(adj)`) — to CSR on the device, by the native sweeps `gcn_dense_to_csr_count` /
+        `gcn_dense_to_csr_fill`: no COO indices, no sort.  `adj` is a 2-D tensor or array (a float64 `np.load` result
+        included); it goes to the device as fp32.  A view with unit column stride is read in place, at its row pitch.
+          greater_than=t    keep the entries a > t (ordinary comparison: NaN dropped); default: the non-zeros, -0 and
+                            +0 dropped and NaN kept, torch.nonzero's rule.
+          keep_per_row=K    of every row only its K strongest entries (K >= 1; K >= n_cols caps nothing): those above
+                            the row's K-th largest, then the lowest columns equal to it, in the selection order of
+                            select.kth_largest (-0 is +0, NaN above +inf) — and of these, the ones the value rule
+                            keeps.  The thresholds come from the radix select in chunks of windows whose workspace
+                            stays at or under 256 MiB.
+          symmetrize        the union of the kept pattern with its transpose; a mirrored pair keeps the larger value
+                            (one from_coo(reduce="max"), the idiom of from_edge_list).  Square matrices only.
+          normalize         False; True or "row" = row_normalize_(); "sym" = sym_normalize_().  No self-loops are
+                            added: a co-visit matrix BᵀB carries its own diagonal.
+          share_transpose   calls share_transpose() on the result.
+        One host read, of the 8-byte entry count (as from_coo); the row pointer is int32 below 2³¹ − 1 entries."""
+        if isinstance(normalize, str) and normalize not in ("row", "sym"):
+            raise RuntimeError(f'from_dense: normalize must be True, False, "row" or "sym", got {normalize!r}')
+        adj = torch.as_tensor(adj)
+        if adj.layout != torch.strided or adj.dim() != 2:
+            raise RuntimeError(f"from_dense: expected a dense 2-D matrix, got {adj.layout} {tuple(adj.shape)}")
+        device = torch.device(device) if device is not None else adj.device
+        adj = adj.to(device=device, dtype=torch.float32)
+        _require_cuda(adj, "the dense adjacency")
+        n_rows, n_cols = int(adj.shape[0]), int(adj.shape[1])
+        if symmetrize and n_rows != n_cols:
+            raise RuntimeError(f"from_dense: symmetrize needs a square matrix, got {tuple(adj.shape)}")
+        keep = None
+        if keep_per_row is not None:
+            if int(keep_per_row) < 1:
+                raise RuntimeError(f"from_dense: keep_per_row must be at least 1, got {keep_per_row}")
+            keep = int(keep_per_row) if int(keep_per_row) < n_cols else None
+        rule = _native.GCN_DENSE_NONZERO if greater_than is None else _native.GCN_DENSE_GREATER
+        rowptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=device)
+        nnz = 0
+        if n_rows and n_cols:
+            if keep is not None or adj.stride(1) != 1 or adj.stride(0) < n_cols:
+                adj = adj.contiguous()     # (the select reads contiguous windows)
+            thr = count_gt = None
+            if keep is not None:
+                from . import select
+                per_window = _native.lib().gcn_select_workspace_bytes(n_cols, 1)
+                step = max(1, min(65535, (256 << 20) // per_window))
+                parts = [select.kth_largest(adj[r:r + step], keep) for r in range(0, n_rows, step)]
+                thr = torch.cat([p[0] for p in parts])
+                count_gt = torch.cat([p[1] for p in parts])
+            head = (adj.data_ptr(), adj.stride(0), n_rows, n_cols, rule,
+                    0.0 if greater_than is None else float(greater_than),
+                    thr.data_ptr() if keep is not None else None,
+                    count_gt.data_ptr() if keep is not None else None, keep or 0)
+            row_count = torch.empty(n_rows, dtype=torch.int32, device=device)
+            _native.launch("gcn_dense_to_csr_count", device, *head, row_count.data_ptr())
+            rowptr[1:] = torch.cumsum(row_count, 0, dtype=torch.int64)
+            nnz = int(rowptr[-1].item())              # one 8-byte read: the number of kept entries
+        if nnz < 2 ** 31 - 1 and not _rowptr_is64:
+            rowptr = rowptr.to(torch.int32)
+        col = torch.empty(nnz, dtype=torch.int32, device=device)
+        val = torch.empty(nnz, dtype=torch.float32, device=device)
+        if nnz:
+            _native.launch("gcn_dense_to_csr_fill", device, *head, rowptr.data_ptr(),
+                           int(rowptr.dtype == torch.int64), col.data_ptr(), val.data_ptr())
+        g = cls(rowptr, col, val, (n_rows, n_cols), validate=False, **kw)
+        if symmetrize:
+            r, c, v = g.coo()
+            g = cls.from_coo(torch.cat([r, c]), torch.cat([c, r]), torch.cat([v, v]), (n_rows, n_cols),
+                             reduce="max", **kw)
+        if normalize == "sym":             # (True == "sym" is False: True keeps meaning "row")
+            g.sym_normalize_()
+        elif normalize:
+            g.row_normalize_()
+        if share_transpose:
+            g.share_transpose()
+        return g
+
     def coo(self):
         """(row int64, col int64, val) of the stored entries, in CSR order."""
         deg = (self.rowptr[1:] - self.rowptr[:-1]).to(torch.int64)
         row = torch.repeat_interleave(torch.arange(self.shape[0], device=self.device), deg)
         return row, self.col.to(torch.int64), self.val
 
+    def to_dense(self):
+        """The stored entries as a dense fp32 [n_rows, n_cols] tensor on the device, bit for bit (plain torch
+        indexing; the matrix must hold no duplicate entries).  For tests, and for looking at a sparsification."""
+        out = torch.zeros(self.shape, dtype=torch.float32, device=self.device)
+        row, col, val = self.coo()
+        out[row, col] = val
+        return out
+
+    @property
+    def density(self):
+        """nnz / (n_rows · n_cols); 0 for a matrix without elements."""
+        cells = self.shape[0] * self.shape[1]
+        return self.nnz / cells if cells else 0.0
+
     @classmethod
     def from_torch(cls, adj, device=None, **kw):
-        """torch sparse COO (the reference's layout, utils.py:414) or sparse CSR tensor."""
+        """torch sparse COO (the reference's layout, utils.py:414) or sparse CSR tensor; a strided (dense) tensor goes
+        through from_dense with its defaults."""
         device = torch.device(device) if device is not None else adj.device
+        if adj.layout == torch.strided:
+            return cls.from_dense(adj, device=device, **kw)
         if adj.layout == torch.sparse_coo:
             idx, val = adj._indices(), adj._values()
             return cls.from_coo(idx[0], idx[1], val, adj.shape, device=device,
