@@ -131,7 +131,8 @@ int gcn_plan_count_host(const void *rowptr_host, int rowptr_is64, int64_t n_rows
  * Planner, pass 2: fill caller-allocated HOST arrays (sizes from pass 1):
  *   items[2*n_items], chunk_row[n_chunks], chunk_e0[n_chunks], long_row[n_long],
  *   long_chunk0[n_long+1].  The caller copies them to the device and points a gcn_csr_plan
- *   at the copies.
+ *   at the copies.  items and long_chunk0 are never NULL; chunk_row / chunk_e0 may be NULL only
+ *   with n_chunks == 0 and long_row only with n_long == 0 (GCN_E_BADARG otherwise).
  */
 int gcn_plan_fill_host(const void *rowptr_host, int rowptr_is64, int64_t n_rows,
                        int32_t item_cost, int32_t long_thresh, int32_t *items, int64_t n_items,

@@ -12,7 +12,8 @@ ROOT = os.path.dirname(HERE)
 SRCS = [os.path.join(HERE, "csrc", f) for f in ("gcn_spmm.hip", "gcn_ingest.hip", "gcn_gemm.hip", "gcn_plan.hip", "gcn_pack.hip",
                                                 "gcn_norm.hip", "gcn_select.hip", "gcn_eval.hip", "gcn_head.hip",
                                                 "gcn_rows.hip", "gcn_normlin.hip", "gcn_symmetric.hip",
-                                                "gcn_agglin.hip", "gcn_dense.hip")]
+                                                "gcn_agglin.hip", "gcn_dense.hip", "gcn_backward.hip",
+                                                "gcn_host.hip", "gcn_error.hip")]
 OUT = os.path.join(HERE, "csrc", "libgcn_spmm.so")
 ARCH = "gfx950"
 

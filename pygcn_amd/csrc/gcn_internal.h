@@ -17,7 +17,7 @@
 // ================================================================================================
 // host side
 // ================================================================================================
-// error reporting (one gcn_last_error() for the whole library): defined in gcn_spmm.hip, with the thread-local
+// error reporting (one gcn_last_error() for the whole library): defined in gcn_error.hip, with the thread-local
 // message buffer
 int gcn_internal_fail(int code, const char *msg);
 int gcn_internal_fail_hip(int hip_error, const char *where);
@@ -41,6 +41,8 @@ static inline float gcn_dropout_scale16(uint32_t thresh)
 namespace {
 
 typedef uint16_t bf16_t;                 // raw bf16 bits
+
+constexpr int kWave = 64;                // lanes of a wavefront; the most rows a row-batch item of the plan holds
 
 // "<who>: <what>" as the library's last error; returns code
 [[maybe_unused]] int bad(const char *who, int code, const char *what)
@@ -176,6 +178,28 @@ template <> struct Lane<bf16_t> {
         Raw r = {pack_bf16x2(x[0], x[1]), pack_bf16x2(x[2], x[3]), pack_bf16x2(x[4], x[5]),
                  pack_bf16x2(x[6], x[7])};
         return r;
+    }
+};
+
+// Elem<T, VEC>: how VEC elements of T travel between memory and fp32 registers.  The 16-byte forms are Lane<T>; the
+// scalar forms serve the kernels that also take rows no 16-byte lane fits (gcn_spmm.hip, gcn_backward.hip)
+template <typename T, int VEC> struct Elem;
+template <> struct Elem<float, 4> : Lane<float> {};
+template <> struct Elem<bf16_t, 8> : Lane<bf16_t> {};
+template <> struct Elem<float, 1> {
+    typedef float Raw;
+    static __device__ __forceinline__ void unpack(const Raw &r, float (&x)[1]) { x[0] = r; }
+    static __device__ __forceinline__ Raw pack(const float (&x)[1]) { return x[0]; }
+};
+template <> struct Elem<bf16_t, 1> {
+    typedef bf16_t Raw;
+    static __device__ __forceinline__ void unpack(const Raw &r, float (&x)[1])
+    {
+        x[0] = __uint_as_float(((uint32_t)r) << 16);
+    }
+    static __device__ __forceinline__ Raw pack(const float (&x)[1])
+    {
+        return (bf16_t)(pack_bf16x2(x[0], 0.f) & 0xffffu);
     }
 };
 

@@ -25,7 +25,7 @@
 // 5 FP64 instructions per element pair loaded, on a part whose FP64 vector rate is half its FP32 one:
 // the sweeps stay HBM-bound (DESIGN.md has the times).  sum_g / sum_gxhat (dbeta / dgamma) stay fp32 [F].
 //
-// Geometry of every sweep (that of bwd_colsum_kernel, gcn_spmm.hip): a 256-thread block owns a
+// Geometry of every sweep (that of bwd_colsum_kernel, gcn_backward.hip): a 256-thread block owns a
 // contiguous slab of rows; thread t owns the 16 bytes (V = 4 fp32 / 8 bf16 columns) at column group
 // t % CG (CG = F / V) of every (256 / CG)-th row of the slab, so its per-column constants live in
 // registers for the whole slab.

@@ -24,7 +24,6 @@
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kRowsPerBlock = 4;          // one wave per row, 4 waves per workgroup
 
 __device__ __forceinline__ int below(unsigned long long m)      // set bits of m in lanes below this one

@@ -3,7 +3,7 @@
 // SURVEY §8 row f4.  The schedule (struct gcn_csr_plan, include/gcn_spmm.h) is what the prepared
 // adjacency carries instead of the torch sparse tensor the reference builds once at load time
 // (pygcn/utils.py:407-414) and hands to every GraphConvolution.forward (pygcn/layers.py:32).
-// gcn_plan_{count,fill}_host walk the row pointer on the CPU; at config C5 that is a 200 MB
+// gcn_plan_{count,fill}_host (gcn_host.hip, plan_walk) walk the row pointer on the CPU; at config C5 that is a 200 MB
 // device->host copy and a 50-million-step sequential loop.  This file produces the SAME schedule,
 // array for array, without the row pointer ever leaving HBM.
 //

@@ -1,6 +1,10 @@
 // gcn_spmm.hip — CSR SpMM for the GraphConvolution hot path, written for gfx950 (MI355X, CDNA4).
 //
-// Implements the C-ABI of include/gcn_spmm.h.  What it replaces in the reference:
+// The sparse kernels over a gcn_csr_plan of the C-ABI of include/gcn_spmm.h: the forward product (gcn_spmm_csr*) and,
+// at the end of the file and for a reason given there, the SDDMM.  The element-wise backward sweeps are
+// gcn_backward.hip, the host planner and transpose gcn_host.hip, the error state gcn_error.hip.  (bench.py stamps
+// its traffic figures with this file's hash: they describe the product's kernels.)
+// What it replaces in the reference:
 //   torch.spmm(adj, support)          pygcn/layers.py:34      -> gcn_spmm_csr on CSR(adj)
 //   adj.t() @ grad_output (autograd)  pygcn/train.py:157      -> gcn_spmm_csr on CSR(adj^T)
 //   output + self.bias                pygcn/layers.py:35-36   -> fused epilogue
@@ -25,8 +29,6 @@
 #include <algorithm>
 #include <climits>
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <type_traits>
 
 #include "gcn_spmm.h"
@@ -34,24 +36,7 @@
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kWavesPerBlock = 4;
-constexpr int kDefaultItemCost = GCN_DEFAULT_ITEM_COST;
-constexpr int kDefaultLongThresh = GCN_DEFAULT_LONG_THRESH;
-
-thread_local char g_err[256] = "";
-
-int fail(int code, const char *msg)
-{
-    std::snprintf(g_err, sizeof(g_err), "%s", msg);
-    return code;
-}
-
-int fail_hip(hipError_t e, const char *where)
-{
-    std::snprintf(g_err, sizeof(g_err), "%s: %s", where, hipGetErrorString(e));
-    return (int)e;
-}
 
 struct KParams {
     const void *rowptr;
@@ -91,30 +76,6 @@ struct KParams {
     int32_t cskip;              // with cflag: all-zero rows are not stored
     uint32_t *cabsmax;          // optional output: max |stored value| as BITS (atomic max; inf / NaN sort on top)
     const void *packed;         // spmm_wide_packed_kernel: the slots of the rows of B (gcn_rows_pack512 / _pack384)
-};
-
-// ------------------------------------------------------------------------------------------
-// element traits: how VEC elements of T travel between memory and fp32 registers
-// ------------------------------------------------------------------------------------------
-// Elem<T, VEC>: the 16-byte forms are gcn_internal.h's Lane<T>; the scalar forms serve the narrow kernels only
-template <typename T, int VEC> struct Elem;
-template <> struct Elem<float, 4> : Lane<float> {};
-template <> struct Elem<bf16_t, 8> : Lane<bf16_t> {};
-template <> struct Elem<float, 1> {
-    typedef float Raw;
-    static __device__ __forceinline__ void unpack(const Raw &r, float (&x)[1]) { x[0] = r; }
-    static __device__ __forceinline__ Raw pack(const float (&x)[1]) { return x[0]; }
-};
-template <> struct Elem<bf16_t, 1> {
-    typedef bf16_t Raw;
-    static __device__ __forceinline__ void unpack(const Raw &r, float (&x)[1])
-    {
-        x[0] = __uint_as_float(((uint32_t)r) << 16);
-    }
-    static __device__ __forceinline__ Raw pack(const float (&x)[1])
-    {
-        return (bf16_t)(pack_bf16x2(x[0], 0.f) & 0xffffu);
-    }
 };
 
 // Row flags of a row-sparse dense operand are used only when they can pay: a device-side count
@@ -1133,211 +1094,6 @@ __global__ __launch_bounds__(256) void spmm_long_reduce_kernel(KParams p)
 }
 
 // ------------------------------------------------------------------------------------------
-// backward of the fused ReLU + inverted-dropout epilogue: out = relu(z) * mask / (1 - p), so
-// out > 0 <=> (z > 0 and kept), and grad_z = grad_out * scale * [out > 0].  One streaming pass,
-// 16 B per lane, grid-stride (HBM-bound: 2 reads + 1 write per element).
-// ------------------------------------------------------------------------------------------
-template <typename T, int VEC>
-__global__ __launch_bounds__(256) void relu_dropout_bwd_kernel(const T *__restrict__ grad_out,
-                                                               const T *__restrict__ out,
-                                                               T *__restrict__ grad_pre,
-                                                               int64_t n_units, float scale)
-{
-    typedef typename Elem<T, VEC>::Raw Raw;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_units; i += stride) {
-        float g[VEC], o[VEC];
-        Elem<T, VEC>::unpack(((const Raw *)grad_out)[i], g);
-        Elem<T, VEC>::unpack(((const Raw *)out)[i], o);
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) g[k] = o[k] > 0.f ? g[k] * scale : 0.f;
-        ((Raw *)grad_pre)[i] = Elem<T, VEC>::pack(g);
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// the same pass with the column sums of its result (grad_bias = sum over rows of grad_pre,
-// autograd of `output + self.bias`, pygcn/layers.py:35-36) produced on the fly.  A 256-thread
-// block owns a contiguous slab of rows; thread t owns the 4 columns 4*(t % CG) (CG = F/4 column
-// groups) of every (256/CG)-th row, keeps 4 running sums, and the block writes one partial row
-// [F]; a second tiny kernel adds the partial rows in block order (deterministic, no atomics).
-// MODE 0 gives a plain column sum (layer without a fused ReLU), MODE 1 the ReLU / dropout mask,
-// MODE 2 the backward of a fused log_softmax: grad_pre = g - exp(out) * rowsum(g), the row sum by
-// xor-shuffles over the row's CG <= 64 lanes; rows of g that are entirely zero (every vertex
-// outside idx_train) are written as zeros without reading `out`.
-// MODE 3 is MODE 2 for the gradient of a mean NLL loss over ALL rows (F.nll_loss(output, labels),
-// reference pygcn/train.py:153 without the index selection): g has one non-zero per row,
-// g[r][target[r]] = coef, so it is never materialised — grad_pre = coef * (onehot(target[r]) -
-// exp(out)), straight from `out` and the label vector: 2 instead of 4 full-height streams.
-// ------------------------------------------------------------------------------------------
-template <typename T, int VEC, int MODE>
-__global__ __launch_bounds__(256) void bwd_colsum_kernel(const T *__restrict__ grad_out,
-                                                         const T *__restrict__ out,
-                                                         T *__restrict__ grad_pre,
-                                                         float *__restrict__ partial, int64_t n_rows,
-                                                         int F, float scale, int rows_per_block,
-                                                         uint8_t *__restrict__ rowflag,
-                                                         int32_t *__restrict__ nnz_rows, int skip,
-                                                         const int64_t *__restrict__ target,
-                                                         const float *__restrict__ coef)
-{
-    typedef typename Elem<T, VEC>::Raw Raw;
-    __shared__ float red[256 * VEC];
-    const float cf = MODE == 3 ? *coef : 0.f;
-    const int CG = F / VEC, RL = 256 / CG;         // column groups (16 B each), row lanes
-    const int cg = threadIdx.x % CG, rl = threadIdx.x / CG;
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-    const int64_t r1 = min(r0 + (int64_t)rows_per_block, n_rows);
-    float acc[VEC];
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
-    int nz_count = 0;
-    // (measured on MI355X: unroll 2 / 4 and 8192 slabs change nothing (+-1 %): the pass already runs at
-    //  the device's mixed read+write rate, 5.5 TB/s)
-#pragma unroll 1
-    for (int64_t r = r0 + rl; r < r1; r += RL) {
-        const int64_t off = r * F + VEC * cg;
-        float g[VEC];
-        if (MODE != 3) Elem<T, VEC>::unpack(*(const Raw *)(grad_out + off), g);
-        Raw packed = {};
-        if (MODE == 3) {
-            const int64_t t_row = target[r];          // (one address per row: a broadcast load)
-            const int64_t t = t_row - VEC * cg;
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) g[i] = 0.f;
-            if (t_row >= 0) {   // a negative label (torch's ignore_index = -100) is an ignored row: zeros
-                float o[VEC];
-                Elem<T, VEC>::unpack(*(const Raw *)(out + off), o);
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) g[i] = cf * ((t == i ? 1.f : 0.f) - expf(o[i]));
-            }
-            packed = Elem<T, VEC>::pack(g);
-            Elem<T, VEC>::unpack(packed, g);
-        }
-        if (MODE == 1) {
-            // lanes whose 16 bytes of grad_out are all zero produce zeros whatever `out` holds:
-            // they skip its load (row-sparse gradients: most of the `out` traffic disappears)
-            bool gnz = false;
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) gnz |= (g[i] != 0.f);
-            if (gnz) {
-                float o[VEC];
-                Elem<T, VEC>::unpack(*(const Raw *)(out + off), o);
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) g[i] = o[i] > 0.f ? g[i] * scale : 0.f;
-            }
-            packed = Elem<T, VEC>::pack(g);
-            Elem<T, VEC>::unpack(packed, g);   // sums and flags follow the STORED (rounded) values
-        }
-        if (MODE == 2) {
-            float rs = 0.f;
-            bool gnz = false;
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                rs += g[i];
-                gnz |= (g[i] != 0.f);
-            }
-            for (int o2 = 1; o2 < CG; o2 <<= 1) rs += __shfl_xor(rs, o2, 64);
-            const unsigned long long gb = __ballot(gnz);
-            const int ln = threadIdx.x & 63;
-            const unsigned long long gm = CG >= 64 ? ~0ull : (((1ull << CG) - 1) << (ln & ~(CG - 1)));
-            if (gb & gm) {   // uniform over the row's lanes
-                float o[VEC];
-                Elem<T, VEC>::unpack(*(const Raw *)(out + off), o);
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) g[i] -= expf(o[i]) * rs;
-            }
-            packed = Elem<T, VEC>::pack(g);
-            Elem<T, VEC>::unpack(packed, g);
-        }
-        bool any = false;
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-            acc[i] += g[i];
-            any |= (g[i] != 0.f);
-        }
-        bool row_nz = true;
-        if (rowflag != nullptr) {
-            // a row lives in CG <= 64 consecutive lanes of one wave (all active or all inactive
-            // together): its non-zero flag is a slice of the wave's ballot over the active lanes;
-            // the row's first lane writes the byte
-            const unsigned long long b = __ballot(any);
-            const int lane = threadIdx.x & 63;
-            const unsigned long long m = CG >= 64 ? ~0ull : (((1ull << CG) - 1) << (lane & ~(CG - 1)));
-            row_nz = (b & m) != 0;
-            if (cg == 0) {
-                rowflag[r] = row_nz ? 1 : 0;
-                nz_count += row_nz ? 1 : 0;
-            }
-        }
-        // skip mode: all-zero rows of the result are not written (the consumer reads the flagged
-        // rows only) — at the labelled share of the bench that is 84-95 % of the pass's writes
-        if (MODE != 0 && (!skip || row_nz)) *(Raw *)(grad_pre + off) = packed;
-    }
-    if (rowflag != nullptr) {
-        // one atomic per wave: lanes that own rows hold their counts
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) nz_count += __shfl_xor(nz_count, off, 64);
-        if ((threadIdx.x & 63) == 0 && nz_count) atomicAdd(nnz_rows, nz_count);
-    }
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) red[threadIdx.x * VEC + i] = acc[i];
-    __syncthreads();
-    if (rl == 0) {
-        for (int k = 1; k < RL; ++k)   // fixed order
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) acc[i] += red[(k * CG + cg) * VEC + i];
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) partial[(int64_t)blockIdx.x * F + VEC * cg + i] = acc[i];
-    }
-}
-
-// per-row bytes -> bitmap words (1 bit per row; fits the XCD L2 where the byte table does not)
-__global__ __launch_bounds__(256) void pack_row_flags_kernel(const uint8_t *__restrict__ bytes,
-                                                             uint32_t *__restrict__ bits, int64_t n_rows)
-{
-    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t n_words = (n_rows + 31) >> 5;
-    if (w >= n_words) return;
-    uint32_t v = 0;
-    const int64_t r0 = w << 5;
-#pragma unroll 8
-    for (int i = 0; i < 32; ++i)
-        if (r0 + i < n_rows && bytes[r0 + i]) v |= 1u << i;
-    bits[w] = v;
-}
-
-// partial[n_blocks][F] -> colsum[F].  A 1024-thread block owns 32 columns; thread (g, c) adds the
-// partial rows g, g+32, g+64, ... of column c (4 loads in flight), then the 32 group sums are added
-// in group order through LDS: a fixed summation order, so the result is bitwise reproducible.
-__global__ __launch_bounds__(1024) void colsum_finish_kernel(const float *__restrict__ partial,
-                                                             float *__restrict__ colsum, int n_blocks,
-                                                             int F)
-{
-    __shared__ float red[32][33];
-    const int c = threadIdx.x & 31, g = threadIdx.x >> 5;
-    const int f = blockIdx.x * 32 + c;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (f < F) {
-        int b = g;
-        for (; b + 96 < n_blocks; b += 128) {
-            s0 += partial[(int64_t)b * F + f];
-            s1 += partial[(int64_t)(b + 32) * F + f];
-            s2 += partial[(int64_t)(b + 64) * F + f];
-            s3 += partial[(int64_t)(b + 96) * F + f];
-        }
-        for (; b < n_blocks; b += 32) s0 += partial[(int64_t)b * F + f];
-    }
-    red[g][c] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (g == 0 && f < F) {
-        float s = 0.f;
-        for (int k = 0; k < 32; ++k) s += red[k][c];
-        colsum[f] = s;
-    }
-}
-
-// ------------------------------------------------------------------------------------------
 // host-side dispatch
 // ------------------------------------------------------------------------------------------
 // XEPI, the extras of a store: 2 = row flags / maximum (log_softmax or not), 1 = log_softmax alone, 0 = none.
@@ -1403,7 +1159,7 @@ int spmm_typed(const gcn_csr_plan *plan, KParams &kp, hipStream_t s, int slot_by
     // skipping all-zero rows is a per-store decision: only when one store call holds the whole row
     if (kp.cskip && !(F <= kWave || (vec_ok && F / VECW <= kWave))) kp.cskip = 0;
     if (kp.log_softmax && !(F <= kWave || (vec_ok && F / VECW <= kWave)))
-        return fail(GCN_E_BADARG, "gcn_spmm_csr_ep: log_softmax needs the row inside one wavefront "
+        return bad("gcn_spmm_csr_ep", GCN_E_BADARG, "log_softmax needs the row inside one wavefront "
                                   "(F <= 64, or 16-byte aligned operands with F/lane width <= 64)");
     if (kp.n_total > 0) {
         if (kp.packed != nullptr) {
@@ -1440,66 +1196,6 @@ int spmm_typed(const gcn_csr_plan *plan, KParams &kp, hipStream_t s, int slot_by
     return 0;
 }
 
-template <typename IdxT>
-int plan_walk(const IdxT *rp, int64_t n_rows, int item_cost, int long_thresh, int32_t *items,
-              int64_t cap_items, int32_t *chunk_row, int64_t *chunk_e0, int64_t cap_chunks,
-              int32_t *long_row, int32_t *long_chunk0, int64_t cap_long, int64_t *n_items,
-              int64_t *n_chunks, int64_t *n_long)
-{
-    const bool fill = items != nullptr;
-    int64_t ni = 0, nc = 0, nl = 0;
-    int64_t ra = 0, cost = 0;
-    auto close = [&](int64_t rb) -> bool {
-        if (rb > ra) {
-            if (fill) {
-                if (ni >= cap_items) return false;
-                items[2 * ni] = (int32_t)ra;
-                items[2 * ni + 1] = (int32_t)rb;
-            }
-            ++ni;
-        }
-        ra = rb;
-        cost = 0;
-        return true;
-    };
-    for (int64_t r = 0; r < n_rows; ++r) {
-        const int64_t deg = (int64_t)rp[r + 1] - (int64_t)rp[r];
-        if (deg < 0) return GCN_E_BADARG;
-        if (deg > long_thresh) {
-            if (!close(r)) return GCN_E_CAPACITY;
-            ra = r + 1;   // the long row belongs to no row-batch item
-            const int64_t k = (deg + long_thresh - 1) / long_thresh;
-            if (fill) {
-                if (nl >= cap_long || nc + k > cap_chunks) return GCN_E_CAPACITY;
-                long_row[nl] = (int32_t)r;
-                long_chunk0[nl] = (int32_t)nc;
-                for (int64_t c = 0; c < k; ++c) {
-                    chunk_row[nc + c] = (int32_t)r;
-                    chunk_e0[nc + c] = (int64_t)rp[r] + c * long_thresh;
-                }
-            }
-            nc += k;
-            ++nl;
-            continue;
-        }
-        const int64_t c = deg + 1;
-        if (r > ra && (cost + c > item_cost || r - ra >= kWave)) {
-            if (!close(r)) return GCN_E_CAPACITY;
-        }
-        cost += c;
-    }
-    if (!close(n_rows)) return GCN_E_CAPACITY;
-    if (fill && long_chunk0 != nullptr) {
-        if (nl > cap_long) return GCN_E_CAPACITY;
-        long_chunk0[nl] = (int32_t)nc;
-    }
-    if (n_items) *n_items = ni;
-    if (n_chunks) *n_chunks = nc;
-    if (n_long) *n_long = nl;
-    return 0;
-}
-
-
 // ------------------------------------------------------------------------------------------
 // SDDMM: out[e] = < G[row(e), :], B[col[e], :] > for every stored entry e of the CSR pattern — the
 // gradient of the adjacency VALUES when a caller sets adj.requires_grad (PyTorch's `mm` derivative
@@ -1510,6 +1206,13 @@ int plan_walk(const IdxT *rp, int64_t n_rows, int item_cost, int long_thresh, in
 // the row of G it works on in registers where the row fits one wave instruction, gathers U = 4
 // rows of B at a time (16 B per lane, row address wave-uniform) and reduces the 4 partial dot
 // products across the wave.  Gather-bound like the product: nnz·(F·s) + n·(F·s) bytes.
+//
+// WHY IT LIVES IN THIS FILE, next to the product it is no part of: sddmm_kernel hands Lane<float>::unpack a reference
+// straight into global memory.  As long as one kernel of the translation unit does, LLVM's argument promotion leaves
+// that helper's signature alone; without one (the product's own kernels unpack registers only) it passes the 16 bytes
+// by value, the helper is inlined in another form, and all 42 fp32 lane instantiations of spmm_narrow_kernel compile
+// to other instructions (profiles/spmm_split_isa.md §1).  Whoever moves this kernel out has those 42
+// to measure again.
 // ------------------------------------------------------------------------------------------
 struct SddmmParams {
     const void *rowptr;
@@ -1585,54 +1288,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void sddmm_kernel(SddmmParam
 
 }   // namespace
 
-// shared with the other .hip files (declared in gcn_internal.h)
-int gcn_internal_fail(int code, const char *msg) { return fail(code, msg); }
-int gcn_internal_fail_hip(int hip_error, const char *where)
-{
-    return fail_hip((hipError_t)hip_error, where);
-}
-
 extern "C" {
-
-int gcn_abi_version(void) { return GCN_ABI_VERSION; }
-
-const char *gcn_last_error(void) { return g_err; }
-
-int gcn_plan_count_host(const void *rowptr_host, int rowptr_is64, int64_t n_rows,
-                        int32_t item_cost, int32_t long_thresh, int64_t *n_items,
-                        int64_t *n_chunks, int64_t *n_long)
-{
-    if (rowptr_host == nullptr || n_rows < 0 || n_rows >= INT32_MAX)
-        return fail(GCN_E_BADARG, "gcn_plan_count_host: bad rowptr / n_rows");
-    if (item_cost <= 0) item_cost = kDefaultItemCost;
-    if (long_thresh <= 0) long_thresh = kDefaultLongThresh;
-    int rc = pick_index(rowptr_is64 != 0, [&](auto i) {
-        return plan_walk((const typename decltype(i)::type *)rowptr_host, n_rows, item_cost, long_thresh, nullptr, 0,
-                         nullptr, nullptr, 0, nullptr, nullptr, 0, n_items, n_chunks, n_long);
-    });
-    return rc ? fail(rc, "gcn_plan_count_host: rowptr is not monotone") : 0;
-}
-
-int gcn_plan_fill_host(const void *rowptr_host, int rowptr_is64, int64_t n_rows,
-                       int32_t item_cost, int32_t long_thresh, int32_t *items, int64_t n_items,
-                       int32_t *chunk_row, int64_t *chunk_e0, int64_t n_chunks,
-                       int32_t *long_row, int32_t *long_chunk0, int64_t n_long)
-{
-    if (rowptr_host == nullptr || n_rows < 0 || n_rows >= INT32_MAX || items == nullptr ||
-        long_chunk0 == nullptr)
-        return fail(GCN_E_BADARG, "gcn_plan_fill_host: null output or bad n_rows");
-    if (item_cost <= 0) item_cost = kDefaultItemCost;
-    if (long_thresh <= 0) long_thresh = kDefaultLongThresh;
-    int64_t ni = 0, nc = 0, nl = 0;
-    int rc = pick_index(rowptr_is64 != 0, [&](auto i) {
-        return plan_walk((const typename decltype(i)::type *)rowptr_host, n_rows, item_cost, long_thresh, items,
-                         n_items, chunk_row, chunk_e0, n_chunks, long_row, long_chunk0, n_long, &ni, &nc, &nl);
-    });
-    if (rc) return fail(rc, "gcn_plan_fill_host: output arrays too small or rowptr not monotone");
-    if (ni != n_items || nc != n_chunks || nl != n_long)
-        return fail(GCN_E_CAPACITY, "gcn_plan_fill_host: sizes differ from gcn_plan_count_host");
-    return 0;
-}
 
 size_t gcn_spmm_workspace_bytes(const gcn_csr_plan *plan, int64_t F)
 {
@@ -1649,29 +1305,29 @@ static int spmm_csr_impl(const gcn_csr_plan *plan, int dtype, const void *B, int
     const int relu = ep ? ep->relu : 0;
     const float drop_p = ep ? ep->dropout_p : 0.f;
     if (!(drop_p >= 0.f && drop_p < 1.f))
-        return fail(GCN_E_BADARG, "gcn_spmm_csr_ep: dropout_p must be in [0, 1)");
-    if (plan == nullptr) return fail(GCN_E_BADARG, "gcn_spmm_csr_ep: plan is NULL");
+        return bad("gcn_spmm_csr_ep", GCN_E_BADARG, "dropout_p must be in [0, 1)");
+    if (plan == nullptr) return bad("gcn_spmm_csr_ep", GCN_E_BADARG, "plan is NULL");
     if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16)
-        return fail(GCN_E_BADARG, "gcn_spmm_csr_ep: unknown dtype");
+        return bad("gcn_spmm_csr_ep", GCN_E_BADARG, "unknown dtype");
     if (plan->n_rows < 0 || plan->n_cols < 0 || plan->nnz < 0 || F < 0 || F > INT32_MAX)
-        return fail(GCN_E_BADARG, "gcn_spmm_csr_ep: negative size");
+        return bad("gcn_spmm_csr_ep", GCN_E_BADARG, "negative size");
     if (plan->n_rows == 0 || F == 0) return 0;
     if (C == nullptr || (B == nullptr && plan->nnz > 0 && !(ep && ep->b2 && ep->b_split == 0)))
-        return fail(GCN_E_BADARG, "gcn_spmm_csr_ep: B or C is NULL");
-    if (ldb < F || ldc < F) return fail(GCN_E_BADARG, "gcn_spmm_csr_ep: ldb/ldc smaller than F");
+        return bad("gcn_spmm_csr_ep", GCN_E_BADARG, "B or C is NULL");
+    if (ldb < F || ldc < F) return bad("gcn_spmm_csr_ep", GCN_E_BADARG, "ldb/ldc smaller than F");
     if (ldb * 4 >= ((int64_t)1 << 32))
-        return fail(GCN_E_BADARG, "gcn_spmm_csr_ep: row stride of B must be below 4 GiB");
+        return bad("gcn_spmm_csr_ep", GCN_E_BADARG, "row stride of B must be below 4 GiB");
     if (plan->rowptr == nullptr || plan->items == nullptr ||
         (plan->nnz > 0 && (plan->col == nullptr || plan->val == nullptr)))
-        return fail(GCN_E_BADARG, "gcn_spmm_csr_ep: plan has NULL arrays");
+        return bad("gcn_spmm_csr_ep", GCN_E_BADARG, "plan has NULL arrays");
     if (plan->n_chunks > 0 && (plan->chunk_row == nullptr || plan->chunk_e0 == nullptr ||
                                plan->long_row == nullptr || plan->long_chunk0 == nullptr))
-        return fail(GCN_E_BADARG, "gcn_spmm_csr_ep: plan has long rows but NULL chunk arrays");
+        return bad("gcn_spmm_csr_ep", GCN_E_BADARG, "plan has long rows but NULL chunk arrays");
     if (plan->n_items + plan->n_chunks >= INT32_MAX || plan->n_long >= INT32_MAX)
-        return fail(GCN_E_BADARG, "gcn_spmm_csr_ep: schedule too large");
+        return bad("gcn_spmm_csr_ep", GCN_E_BADARG, "schedule too large");
     const size_t need = gcn_spmm_workspace_bytes(plan, F);
     if (need > 0 && (workspace == nullptr || workspace_bytes < need))
-        return fail(GCN_E_WORKSPACE, "gcn_spmm_csr_ep: workspace too small");
+        return bad("gcn_spmm_csr_ep", GCN_E_WORKSPACE, "workspace too small");
 
     KParams kp;
     kp.packed = packed;
@@ -1693,7 +1349,7 @@ static int spmm_csr_impl(const gcn_csr_plan *plan, int dtype, const void *B, int
     kp.n_total = (int32_t)(plan->n_items + plan->n_chunks);
     kp.n_chunks = (int32_t)plan->n_chunks;
     kp.n_long = (int32_t)plan->n_long;
-    kp.long_thresh = plan->long_thresh > 0 ? plan->long_thresh : kDefaultLongThresh;
+    kp.long_thresh = plan->long_thresh > 0 ? plan->long_thresh : GCN_DEFAULT_LONG_THRESH;
     kp.relu = relu ? 1 : 0;
     // keep iff rand16 >= round(p * 2^16)  (p = 0 -> threshold 0 -> dropout off)
     kp.drop_thresh = gcn_dropout_threshold16(drop_p);
@@ -1709,14 +1365,14 @@ static int spmm_csr_impl(const gcn_csr_plan *plan, int dtype, const void *B, int
     kp.ldb2 = ep && ep->b2 ? ep->ldb2 : 0;
     kp.b_split = (ep && ep->b2) ? (int32_t)std::min<int64_t>(ep->b_split, INT32_MAX) : INT32_MAX;
     if (ep && ep->b2 && (ep->b_split < 0 || ep->ldb2 < F || ep->ldb2 * 4 >= ((int64_t)1 << 32)))
-        return fail(GCN_E_BADARG, "gcn_spmm_csr_ep: bad second block of B");
+        return bad("gcn_spmm_csr_ep", GCN_E_BADARG, "bad second block of B");
     kp.bflag = ep ? ep->b_row_nonzero : nullptr;
     kp.bnnz = ep ? ep->b_nnz_rows : nullptr;
     if (kp.bflag == nullptr || kp.bnnz == nullptr) kp.bflag = nullptr, kp.bnnz = nullptr;
     kp.cflag = ep ? ep->c_row_nonzero : nullptr;
     kp.log_softmax = (ep && ep->log_softmax) ? 1 : 0;
     if (kp.log_softmax && (relu || drop_p > 0.f))
-        return fail(GCN_E_BADARG, "gcn_spmm_csr_ep: log_softmax cannot be combined with relu / dropout");
+        return bad("gcn_spmm_csr_ep", GCN_E_BADARG, "log_softmax cannot be combined with relu / dropout");
     kp.n_cols = (int32_t)std::min<int64_t>(plan->n_cols, INT32_MAX);
     hipStream_t s = (hipStream_t)stream;
     return pick_dtype(dtype, [&](auto t) {
@@ -1735,18 +1391,18 @@ int gcn_spmm_csr_ep(const gcn_csr_plan *plan, int dtype, const void *B, int64_t 
 int gcn_spmm_csr_packed(const gcn_csr_plan *plan, const uint32_t *slots, const float *B, int64_t ldb, float *C,
                         int64_t ldc, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (slots == nullptr || B == nullptr) return fail(GCN_E_BADARG, "gcn_spmm_csr_packed: slots or B is NULL");
+    if (slots == nullptr || B == nullptr) return bad("gcn_spmm_csr_packed", GCN_E_BADARG, "slots or B is NULL");
     if ((((uintptr_t)slots) | ((uintptr_t)B) | ((uintptr_t)C)) % 16 != 0 || ldb % 4 != 0 || ldc % 4 != 0)
-        return fail(GCN_E_ALIGN, "gcn_spmm_csr_packed: 16-byte aligned slots and rows required");
+        return bad("gcn_spmm_csr_packed", GCN_E_ALIGN, "16-byte aligned slots and rows required");
     return spmm_csr_impl(plan, GCN_DTYPE_F32, B, ldb, C, ldc, 256, nullptr, workspace, workspace_bytes, stream, slots);
 }
 
 int gcn_spmm_csr_packed384(const gcn_csr_plan *plan, const uint32_t *slots, const float *B, int64_t ldb, float *C,
                            int64_t ldc, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (slots == nullptr || B == nullptr) return fail(GCN_E_BADARG, "gcn_spmm_csr_packed384: slots or B is NULL");
+    if (slots == nullptr || B == nullptr) return bad("gcn_spmm_csr_packed384", GCN_E_BADARG, "slots or B is NULL");
     if ((((uintptr_t)slots) | ((uintptr_t)B) | ((uintptr_t)C)) % 16 != 0 || ldb % 4 != 0 || ldc % 4 != 0)
-        return fail(GCN_E_ALIGN, "gcn_spmm_csr_packed384: 16-byte aligned slots and rows required");
+        return bad("gcn_spmm_csr_packed384", GCN_E_ALIGN, "16-byte aligned slots and rows required");
     return spmm_csr_impl(plan, GCN_DTYPE_F32, B, ldb, C, ldc, 256, nullptr, workspace, workspace_bytes, stream, slots,
                          384);
 }
@@ -1761,143 +1417,25 @@ int gcn_spmm_csr(const gcn_csr_plan *plan, int dtype, const void *B, int64_t ldb
     return gcn_spmm_csr_ep(plan, dtype, B, ldb, C, ldc, F, &ep, workspace, workspace_bytes, stream);
 }
 
-int gcn_relu_dropout_backward(int dtype, const void *grad_out, const void *out, void *grad_pre,
-                              int64_t n_elems, float scale, void *stream)
-{
-    if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16)
-        return fail(GCN_E_BADARG, "gcn_relu_dropout_backward: unknown dtype");
-    if (n_elems < 0) return fail(GCN_E_BADARG, "gcn_relu_dropout_backward: negative size");
-    if (n_elems == 0) return 0;
-    if (grad_out == nullptr || out == nullptr || grad_pre == nullptr)
-        return fail(GCN_E_BADARG, "gcn_relu_dropout_backward: NULL pointer");
-    const int64_t per = lane_elems(dtype);
-    const bool vec = (n_elems % per == 0) && (((uintptr_t)grad_out | (uintptr_t)out |
-                                                (uintptr_t)grad_pre) % 16 == 0);
-    const int64_t n_units = vec ? n_elems / per : n_elems;
-    const unsigned blocks = (unsigned)std::min<int64_t>((n_units + 255) / 256, 256 * 8 * 4);
-    hipStream_t s = (hipStream_t)stream;
-    pick_dtype(dtype, [&](auto t) {
-        typedef typename decltype(t)::type T;
-        pick_int<Lane<T>::V, 1>(vec ? Lane<T>::V : 1, [&](auto v) {
-            hipLaunchKernelGGL((relu_dropout_bwd_kernel<T, decltype(v)::value>), dim3(blocks), dim3(256), 0, s,
-                               (const T *)grad_out, (const T *)out, (T *)grad_pre, n_units, scale);
-        });
-    });
-    return launched("relu_dropout_backward launch");
-}
-
-size_t gcn_bwd_colsum_workspace_bytes(int64_t n_rows, int64_t F, int dtype)
-{
-    if (n_rows <= 0 || !lane_width_ok(F, dtype)) return 0;
-    // partial column sums + one byte per row (staging for the row bitmap)
-    return (size_t)RowSlabs(n_rows).blocks * (size_t)F * sizeof(float) + (((size_t)n_rows + 15) & ~(size_t)15);
-}
-
-static int bwd_colsum_impl(const char *who, int mode, int dtype, const void *grad_out, const void *out,
-                           void *grad_pre, float *colsum, int64_t n_rows, int64_t F, float scale,
-                           uint32_t *row_bits, int32_t *nnz_rows, int skip_zero_rows,
-                           void *workspace, size_t workspace_bytes, void *stream,
-                           const int64_t *target = nullptr, const float *coef = nullptr)
-{
-    if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16) return bad(who, GCN_E_BADARG, "unknown dtype");
-    if ((row_bits == nullptr) != (nnz_rows == nullptr))
-        return bad(who, GCN_E_BADARG, "row_bits and nnz_rows go together");
-    const int64_t vec = lane_elems(dtype);
-    if (n_rows < 0 || !lane_width_ok(F, dtype))
-        return bad(who, GCN_E_BADARG, "F must be a multiple of the 16-byte lane width with F/width dividing 256");
-    if (mode >= 2 && F / vec > 64)
-        return bad(who, GCN_E_BADARG, "a row must fit one wavefront (F / lane width <= 64)");
-    if (row_bits != nullptr && F / vec > 64)   // a row spans several wavefronts: no per-row ballot
-        return bad(who, GCN_E_BADARG, "row_bits / nnz_rows need F / lane width <= 64 (pass NULL for wider rows)");
-    if (skip_zero_rows && (row_bits == nullptr || mode == 0))
-        return bad(who, GCN_E_BADARG, "skip_zero_rows needs the row bitmap outputs and a result tensor");
-    if (colsum == nullptr || (grad_out == nullptr && mode != 3) || (out != nullptr && grad_pre == nullptr)
-        || (mode == 3 && (target == nullptr || coef == nullptr || out == nullptr)))
-        return bad(who, GCN_E_BADARG, "NULL pointer");
-    hipStream_t s = (hipStream_t)stream;
-    if (nnz_rows != nullptr) {
-        hipError_t e = hipMemsetAsync(nnz_rows, 0, sizeof(int32_t), s);
-        if (e != hipSuccess) return fail_hip(e, who);
-    }
-    if (n_rows == 0) {
-        hipError_t e = hipMemsetAsync(colsum, 0, (size_t)F * sizeof(float), s);
-        return e == hipSuccess ? 0 : fail_hip(e, who);
-    }
-    const size_t need = gcn_bwd_colsum_workspace_bytes(n_rows, F, dtype);
-    if (workspace == nullptr || workspace_bytes < need) return bad(who, GCN_E_WORKSPACE, "workspace too small");
-    if (((uintptr_t)grad_out | (uintptr_t)out | (uintptr_t)grad_pre | (uintptr_t)workspace) % 16 != 0)
-        return bad(who, GCN_E_ALIGN, "16-byte alignment required");
-    const RowSlabs sl(n_rows);
-    uint8_t *row_nonzero = row_bits ? (uint8_t *)workspace + (size_t)sl.blocks * (size_t)F * sizeof(float)
-                                    : nullptr;
-    const dim3 grid((unsigned)sl.blocks), block(256);
-    float *part = (float *)workspace;
-    pick_dtype(dtype, [&](auto t) {
-        typedef typename decltype(t)::type T;
-        pick_int<0, 1, 2, 3>(mode, [&](auto m) {
-            hipLaunchKernelGGL((bwd_colsum_kernel<T, Lane<T>::V, decltype(m)::value>), grid, block, 0, s,
-                               (const T *)grad_out, (const T *)out, (T *)grad_pre, part, n_rows, (int)F, scale,
-                               sl.rows_per_block, row_nonzero, nnz_rows, skip_zero_rows ? 1 : 0, target, coef);
-        });
-    });
-    hipLaunchKernelGGL(colsum_finish_kernel, dim3((unsigned)((F + 31) / 32)), dim3(1024), 0, s,
-                       (const float *)workspace, colsum, (int)sl.blocks, (int)F);
-    if (row_bits != nullptr)
-        hipLaunchKernelGGL(pack_row_flags_kernel, dim3((unsigned)((((n_rows + 31) >> 5) + 255) / 256)),
-                           dim3(256), 0, s, (const uint8_t *)row_nonzero, row_bits, n_rows);
-    return launched(who);
-}
-
-int gcn_relu_dropout_backward_colsum(int dtype, const void *grad_out, const void *out, void *grad_pre,
-                                     float *colsum, int64_t n_rows, int64_t F, float scale,
-                                     uint32_t *row_bits, int32_t *nnz_rows, int skip_zero_rows,
-                                     void *workspace, size_t workspace_bytes, void *stream)
-{
-    return bwd_colsum_impl("gcn_relu_dropout_backward_colsum", out != nullptr ? 1 : 0, dtype, grad_out,
-                           out, grad_pre, colsum, n_rows, F, scale, row_bits, nnz_rows, skip_zero_rows,
-                           workspace, workspace_bytes, stream);
-}
-
-int gcn_log_softmax_backward_colsum(int dtype, const void *grad_out, const void *out, void *grad_pre,
-                                    float *colsum, int64_t n_rows, int64_t F, uint32_t *row_bits,
-                                    int32_t *nnz_rows, int skip_zero_rows, void *workspace,
-                                    size_t workspace_bytes, void *stream)
-{
-    if (out == nullptr)
-        return fail(GCN_E_BADARG, "gcn_log_softmax_backward_colsum: NULL pointer");
-    return bwd_colsum_impl("gcn_log_softmax_backward_colsum", 2, dtype, grad_out, out, grad_pre, colsum,
-                           n_rows, F, 1.f, row_bits, nnz_rows, skip_zero_rows, workspace,
-                           workspace_bytes, stream);
-}
-
-int gcn_nll_log_softmax_backward_colsum(int dtype, const int64_t *target, const float *coef,
-                                        const void *out, void *grad_pre, float *colsum, int64_t n_rows,
-                                        int64_t F, void *workspace, size_t workspace_bytes, void *stream)
-{
-    return bwd_colsum_impl("gcn_nll_log_softmax_backward_colsum", 3, dtype, nullptr, out, grad_pre,
-                           colsum, n_rows, F, 1.f, nullptr, nullptr, 0, workspace, workspace_bytes,
-                           stream, target, coef);
-}
-
 int gcn_sddmm_csr(const gcn_csr_plan *plan, int dtype, const void *G, int64_t ldg, const void *B,
                   int64_t ldb, int64_t F, float *out_vals, void *stream)
 {
-    if (plan == nullptr) return fail(GCN_E_BADARG, "gcn_sddmm_csr: plan is NULL");
-    if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16)
-        return fail(GCN_E_BADARG, "gcn_sddmm_csr: unknown dtype");
+    const char *who = "gcn_sddmm_csr";
+    if (plan == nullptr) return bad(who, GCN_E_BADARG, "plan is NULL");
+    if (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16) return bad(who, GCN_E_BADARG, "unknown dtype");
     if (plan->n_rows < 0 || plan->n_cols < 0 || plan->nnz < 0 || F < 0 || F > INT32_MAX)
-        return fail(GCN_E_BADARG, "gcn_sddmm_csr: negative size");
+        return bad(who, GCN_E_BADARG, "negative size");
     if (plan->nnz == 0) return 0;
     if (G == nullptr || B == nullptr || out_vals == nullptr || plan->rowptr == nullptr ||
         plan->col == nullptr || plan->items == nullptr)
-        return fail(GCN_E_BADARG, "gcn_sddmm_csr: NULL pointer");
+        return bad(who, GCN_E_BADARG, "NULL pointer");
     if (plan->n_chunks > 0 && (plan->chunk_row == nullptr || plan->chunk_e0 == nullptr))
-        return fail(GCN_E_BADARG, "gcn_sddmm_csr: plan has long rows but NULL chunk arrays");
-    if (ldg < F || ldb < F) return fail(GCN_E_BADARG, "gcn_sddmm_csr: ldg / ldb smaller than F");
+        return bad(who, GCN_E_BADARG, "plan has long rows but NULL chunk arrays");
+    if (ldg < F || ldb < F) return bad(who, GCN_E_BADARG, "ldg / ldb smaller than F");
     hipStream_t s = (hipStream_t)stream;
     if (F == 0) {
         hipError_t e = hipMemsetAsync(out_vals, 0, (size_t)plan->nnz * sizeof(float), s);
-        return e == hipSuccess ? 0 : fail_hip(e, "gcn_sddmm_csr");
+        return e == hipSuccess ? 0 : gcn_internal_fail_hip((int)e, who);
     }
     SddmmParams sp;
     sp.rowptr = plan->rowptr;
@@ -1913,7 +1451,7 @@ int gcn_sddmm_csr(const gcn_csr_plan *plan, int dtype, const void *G, int64_t ld
     sp.F = (int32_t)F;
     sp.n_total = (int32_t)(plan->n_items + plan->n_chunks);
     sp.n_chunks = (int32_t)plan->n_chunks;
-    sp.long_thresh = plan->long_thresh > 0 ? plan->long_thresh : kDefaultLongThresh;
+    sp.long_thresh = plan->long_thresh > 0 ? plan->long_thresh : GCN_DEFAULT_LONG_THRESH;
     const bool is64 = plan->rowptr_is64 != 0;
     const int64_t vw = lane_elems(dtype), es = 16 / vw;
     const bool vec_ok = (F % vw == 0) && (((uintptr_t)G | (uintptr_t)B) % 16 == 0) &&
@@ -1929,39 +1467,6 @@ int gcn_sddmm_csr(const gcn_csr_plan *plan, int dtype, const void *G, int64_t ld
         });
     });
     return launched("gcn_sddmm_csr launch");
-}
-
-int gcn_csr_transpose_host(const void *rowptr_host, int rowptr_is64, const int32_t *col,
-                           const float *val, int64_t n_rows, int64_t n_cols, void *rowptr_t,
-                           int32_t *col_t, float *val_t)
-{
-    if (rowptr_host == nullptr || rowptr_t == nullptr || n_rows < 0 || n_cols < 0)
-        return fail(GCN_E_BADARG, "gcn_csr_transpose_host: bad arguments");
-    int rc = pick_index(rowptr_is64 != 0, [&](auto i) -> int {
-        typedef typename decltype(i)::type I;
-        const I *rp = (const I *)rowptr_host;
-        I *rpt = (I *)rowptr_t;
-        const int64_t nnz = (int64_t)rp[n_rows];
-        if (nnz > 0 && (col == nullptr || val == nullptr || col_t == nullptr || val_t == nullptr))
-            return GCN_E_BADARG;
-        for (int64_t k = 0; k <= n_cols; ++k) rpt[k] = 0;
-        for (int64_t e = 0; e < nnz; ++e) {
-            if (col[e] < 0 || col[e] >= n_cols) return GCN_E_BADARG;
-            rpt[col[e] + 1]++;
-        }
-        for (int64_t k = 0; k < n_cols; ++k) rpt[k + 1] += rpt[k];
-        for (int64_t i = 0; i < n_rows; ++i) {
-            for (int64_t e = (int64_t)rp[i]; e < (int64_t)rp[i + 1]; ++e) {
-                const int64_t dst = (int64_t)rpt[col[e]]++;
-                col_t[dst] = (int32_t)i;
-                val_t[dst] = val[e];
-            }
-        }
-        for (int64_t k = n_cols; k > 0; --k) rpt[k] = rpt[k - 1];
-        rpt[0] = (I)0;
-        return 0;
-    });
-    return rc ? fail(rc, "gcn_csr_transpose_host: column index out of range or NULL array") : 0;
 }
 
 }   // extern "C"

@@ -185,7 +185,7 @@ def edge_graph(seed=2024):
 
 
 def host_items(rowptr, item_cost, long_thresh):
-    """Python restatement of the planner's rule (plan_walk in gcn_spmm.hip): the row-batch items
+    """Python restatement of the planner's rule (plan_walk in gcn_host.hip): the row-batch items
     [(ra, rb)] and the long rows of a row pointer.  For the tests' own claims about the graph."""
     item_cost = item_cost if item_cost > 0 else 64
     deg = np.diff(np.asarray(rowptr, np.int64))

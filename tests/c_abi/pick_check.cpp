@@ -7,7 +7,7 @@
 #include "gcn_spmm.h"
 #include "gcn_internal.h"
 
-// the two error hooks the header declares (gcn_spmm.hip defines them in the library); nothing here fails
+// the two error hooks the header declares (gcn_error.hip defines them in the library); nothing here fails
 int gcn_internal_fail(int code, const char *) { return code; }
 int gcn_internal_fail_hip(int hip_error, const char *) { return -1000 - hip_error; }
 

@@ -458,6 +458,27 @@ def test_internal_header_picks_in_a_standalone_host_program(tmp_path):
     assert "pick_check ok" in out.stdout
 
 
+def test_host_planner_and_transpose_in_a_standalone_sanitized_program(tmp_path):
+    """tests/c_abi/host_check.cpp drives gcn_plan_count_host / gcn_plan_fill_host / gcn_csr_transpose_host of
+    pygcn_amd/csrc/gcn_host.hip on heap arrays of exactly the sizes the API asks for: the edge shapes of the planner
+    (item caps, the long-row threshold, long rows first / last / adjacent, the defaults) and of the transpose, and
+    every refusal.  The source is compiled INTO the program, host-only, under the address and undefined-behaviour
+    sanitizers (the flags of the pick check above): a write one past an array is a report, not a silent pass as on
+    the numpy buffers of the ctypes tests.  Needs neither the library nor a device."""
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    exe = str(tmp_path / "host_check")
+    subprocess.check_call([hipcc, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-Wall", "-Werror",
+                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "pygcn_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "c_abi", "host_check.cpp"),
+                           os.path.join(ROOT, "pygcn_amd", "csrc", "gcn_host.hip"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "host_check ok" in out.stdout
+
+
 def test_workspace_queries_answer_as_recorded():
     """Every *_workspace_bytes query answers what tests/golden/workspace_bytes.json recorded from the library of
     commit 8f70753 (tools/record_workspace_bytes.py): the sizes are ABI-visible and follow the slab rules, so a change
