@@ -92,7 +92,8 @@ typedef struct gcn_csr_plan {
  * gcn_bn_linear_backward_sums / gcn_bn_linear_backward_apply (ReLU + BatchNorm folded into the next layer's X·W for
  * 32-wide layers).  Also additive to 26: gcn_agg_linear_partial_rows / gcn_agg_linear_forward /
  * gcn_agg_linear_backward (the dense half of an aggregate-first input layer, (A·X)·W + b, for inputs of 4 .. 32
- * columns into a 32-wide layer).
+ * columns into a 32-wide layer).  Also additive to 26: gcn_csr_sample_rows, at most K stored entries per row of a
+ * CSR matrix (neighbour sampling).
  * 25 (round 4, late): new entry point gcn_gemm_atg256_f32_b3_colsum (the
  * weight gradient with the bias gradient Σ G[rows] as a side result); gcn_gemm_atg256_workspace_bytes grew by
  * 1 KiB per workgroup; struct gcn_gemm_epilogue gained keep_bits_out / mask_bits at its END (zero them);
@@ -1085,6 +1086,63 @@ int gcn_dense_to_csr_count(const float *A, int64_t lda, int64_t n_rows, int64_t 
 int gcn_dense_to_csr_fill(const float *A, int64_t lda, int64_t n_rows, int64_t n_cols, int rule, float bound,
                           const float *thr, const int32_t *count_gt, int64_t keep, const void *rowptr, int rowptr_is64,
                           int32_t *col, float *val, void *stream);
+
+/*
+ * Neighbour sampling (pygcn_amd/csrc/gcn_sample.hip; CSRGraph.sample_neighbors): at most K = fanout of the stored
+ * entries of every row of a CSR matrix, as a CSR matrix of its own — the fan-out of GraphSAGE-style training, DropEdge
+ * as its special case.  A per-row segmented select with no sort, NO WORKSPACE and no allocation; all pointers DEVICE,
+ * nothing is read by the host.  Output row r is made from source row s = rows[r] (rows: int64 [m], each in
+ * [0, n_rows) — the CALLER'S duty, it is not checked — any order, repeats allowed), or s = r when rows is NULL.  With
+ * d the number of stored entries of row s:
+ *   d <= K    the row is copied.
+ *   d >  K    exactly K entries are kept: those with the K largest 32-bit KEYS, compared as unsigned integers; on
+ *             equal keys the entry stored earlier wins.
+ * Kept entries come out in their stored order (ascending columns stay ascending), the columns unchanged, the values
+ * bit for bit the stored ones unless rescale is set.  rowptr_out [m + 1] (int32, or int64 with out_is64) is SUPPLIED
+ * by the caller: the exclusive scan of min(d, K), which needs no pass over the entries; col_out / val_out have
+ * rowptr_out[m] entries.  Nothing outside a row's own slots is written for that row, whatever rowptr_out says.
+ *   THE RANDOM WORD of the entry at index e of the SOURCE arrays col / val:
+ *       w(e) = Philox4x32-10(counter = (lo32(e >> 2), hi32(e >> 2), draw_stream, 2), key = (lo32(seed), hi32(seed)))[e & 3]
+ *   — counter word 3 = 2 keeps the stream apart from the dropout's (0) and the race keys' (1).  It depends on
+ *   (seed, draw_stream, e) only: sampling the rows `rows` gives, bit for bit, the rows `rows` of the sample of the
+ *   whole matrix, and no launch shape can change a draw.
+ *   THE KEY, by mode:
+ *       GCN_SAMPLE_UNIFORM     w(e): every K-subset of the row is equally likely.  val takes no part in the choice.
+ *       GCN_SAMPLE_WEIGHT      the selection-order key ("Vertex selection" above: -0 is +0, NaN above +inf) of
+ *                              fp32(double(val) / E), E = -log((w(e) + 0.5) * 2^-32) — the race key of gcn_race_keys:
+ *                              K draws without replacement with probability proportional to the value
+ *                              (Plackett-Luce).  Values must be finite and >= 0, which is NOT checked.  A zero value
+ *                              has the key of +0: zeros are taken last, lowest position first.
+ *       GCN_SAMPLE_STRONGEST   the selection-order key of val: deterministic, seed and draw_stream are ignored.
+ *   keep_diagonal (0 / 1)   the first stored entry of row s with col == s is kept ahead of the key order and counts as
+ *                           one of the K; the other K - 1 are the largest keys of the remaining entries.
+ *   rescale                 GCN_SAMPLE_RESCALE_NONE leaves the values alone.  GCN_SAMPLE_RESCALE_SUM, in rows with
+ *                           d > K only: S = the sum of all stored values of the row, S' = that of the kept ones, both in
+ *                           double; ratio = fp32(S / S'), formed in double and rounded once; every kept value is
+ *                           multiplied by ratio in fp32.  A row whose ratio is not finite (S' = 0) keeps its values.
+ *                           A row-normalised matrix keeps its row sums (the GraphSAGE mean).  The double additions run
+ *                           in a fixed order — a lane's entries in stored order, then the lanes, then the waves — so
+ *                           two runs give the same bytes; a sum in another order can move ratio by one fp32 step only
+ *                           where S / S' lies within a few double steps of an fp32 rounding boundary.
+ * Rows of up to GCN_SAMPLE_WAVE_ROW_MAX entries take one wavefront each, the row in registers (a grid of at most
+ * GCN_SAMPLE_WAVE_SWEEP_ROWS wavefronts strides over the rows); longer rows take one workgroup each, which computes the
+ * keys again in each of its passes.  A row holds fewer than 2^32 entries.  No float atomics.
+ * GCN_E_BADARG, before any launch and without a device: fanout < 1, an unknown mode or rescale, m < 0 or m > 2^40, a
+ * NULL array other than rows with m > 0.  GCN_E_ALIGN: rows or a 64-bit row pointer not 8-byte aligned, another array
+ * not 4-byte aligned.  m = 0 launches nothing and returns 0.
+ * (ABI 26, additive.)
+ */
+#define GCN_SAMPLE_UNIFORM 0
+#define GCN_SAMPLE_WEIGHT 1
+#define GCN_SAMPLE_STRONGEST 2
+#define GCN_SAMPLE_RESCALE_NONE 0
+#define GCN_SAMPLE_RESCALE_SUM 1
+#define GCN_SAMPLE_WAVE_ROW_MAX 253         /* the longest row that one wavefront holds in registers */
+#define GCN_SAMPLE_WAVE_SWEEP_ROWS 65536    /* rows that one sweep of the row-per-wavefront grid covers */
+int gcn_csr_sample_rows(const void *rowptr, int rowptr_is64, const int32_t *col, const float *val, const int64_t *rows,
+                        int64_t m, int64_t fanout, int mode, uint64_t seed, uint32_t draw_stream, int keep_diagonal,
+                        int rescale, const void *rowptr_out, int out_is64, int32_t *col_out, float *val_out,
+                        void *stream);
 
 #ifdef __cplusplus
 }

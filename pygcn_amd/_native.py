@@ -21,6 +21,13 @@ GCN_DTYPE_BF16 = 1
 GCN_DENSE_NONZERO = 0
 GCN_DENSE_GREATER = 1
 GCN_DENSE_SWEEP_ROWS = 8192
+GCN_SAMPLE_UNIFORM = 0
+GCN_SAMPLE_WEIGHT = 1
+GCN_SAMPLE_STRONGEST = 2
+GCN_SAMPLE_RESCALE_NONE = 0
+GCN_SAMPLE_RESCALE_SUM = 1
+GCN_SAMPLE_WAVE_ROW_MAX = 253
+GCN_SAMPLE_WAVE_SWEEP_ROWS = 65536
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 c_i64p = ctypes.POINTER(ctypes.c_int64)
@@ -160,6 +167,7 @@ SIGNATURES = {
     "gcn_agg_linear_backward": (i, [p, p, p, i64, i64, i64, i64, i, p, p, p, i64, p]),
     "gcn_dense_to_csr_count": (i, [p, i64, i64, i64, i, f32, p, p, i64, p, p]),
     "gcn_dense_to_csr_fill": (i, [p, i64, i64, i64, i, f32, p, p, i64, p, i, p, p, p]),
+    "gcn_csr_sample_rows": (i, [p, i, p, p, p, i64, i64, i, ctypes.c_uint64, ctypes.c_uint32, i, i, p, i, p, p, p]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -13,7 +13,7 @@ SRCS = [os.path.join(HERE, "csrc", f) for f in ("gcn_spmm.hip", "gcn_ingest.hip"
                                                 "gcn_norm.hip", "gcn_select.hip", "gcn_eval.hip", "gcn_head.hip",
                                                 "gcn_rows.hip", "gcn_normlin.hip", "gcn_symmetric.hip",
                                                 "gcn_agglin.hip", "gcn_dense.hip", "gcn_backward.hip",
-                                                "gcn_host.hip", "gcn_error.hip")]
+                                                "gcn_sample.hip", "gcn_host.hip", "gcn_error.hip")]
 OUT = os.path.join(HERE, "csrc", "libgcn_spmm.so")
 ARCH = "gfx950"
 

@@ -36,6 +36,14 @@ from pygcn_amd.normlin import relu_batch_norm_linear  # noqa: E402,F401
 # its narrow input layers (4, 8 or 16 columns into 32: pygcn/gnn-over-mlp.py:221-237, policy-generator.py:330-350)
 # evaluated aggregate-first, (adj·x)·W + b, where the input needs no gradient: pygcn_amd/agglin.py
 from pygcn_amd.agglin import aggregate_linear  # noqa: E402,F401
+from pygcn_amd.graph import as_graph  # noqa: E402
+
+
+def sample_neighbors(adj, fanout, **kw):
+    """A fan-out on any adjacency the layers accept (a CSRGraph or a torch sparse tensor on the HIP device): at most
+    `fanout` stored entries per row, as a CSRGraph — `CSRGraph.sample_neighbors`, which documents the keywords
+    (by, seed, stream, rows, keep_diagonal, rescale): pygcn_amd/sampling.py"""
+    return as_graph(adj).sample_neighbors(fanout, **kw)
 
 
 class NLLGrad(torch.Tensor):

@@ -537,6 +537,35 @@ class CSRGraph:
         g.n_unmapped = int(unmapped) if (col_map is not None and total) else 0
         return g
 
+    def sample_neighbors(self, fanout, by="uniform", seed=None, stream=0, rows=None, keep_diagonal=None,
+                         rescale=None):
+        """A fan-out: this matrix with at most K = `fanout` stored entries per row, as a CSRGraph of its own —
+        GraphSAGE-style neighbour sampling (DropEdge as its special case), to be redrawn every step.  Row r of the
+        result is made from row r, or from row rows[r] when `rows` is given (int64, any order, repeats allowed, as
+        take_rows has it); the shape is (n_rows or len(rows), n_cols).  A row of at most K entries is copied; a longer
+        one keeps exactly K, in their stored order, columns unchanged and values bit for bit unless `rescale` is set:
+          by="uniform"     every K-subset of the row is equally likely;
+          by="weight"      K draws without replacement with probability proportional to the value (values finite
+                           and >= 0, NOT checked; zeros are taken last, lowest position first);
+          by="strongest"   the K largest values, ties by lowest position: deterministic, seed and stream ignored —
+                           from_dense(keep_per_row=K)'s rule for strictly positive values.
+          keep_diagonal    the row's first entry on the diagonal is kept ahead of that order and counts as one of the
+                           K.  Default: on for a square matrix, off otherwise (True raises there).
+          rescale="sum"    the kept values of a cut row are multiplied by fp32(S / S'), S the sum of the row and S' of
+                           the kept entries, both in double: a row-normalised matrix keeps its row sums (the
+                           GraphSAGE mean).  Rows with S' = 0 keep their values.
+        The draw is a function of (seed, stream, position of the entry in this graph's arrays) only — the stream
+        include/gcn_spmm.h states under "Neighbour sampling" — so `g.sample_neighbors(K, seed=s, rows=R)` is bitwise
+        `g.sample_neighbors(K, seed=s).take_rows(R)`, and two calls with the same (seed, stream) agree bit for bit.
+        Pass the step number as `stream` for a fresh sample per step.  seed=None draws a 64-bit seed from the device's
+        generator as sample_without_replacement does (torch.manual_seed reproduces a run).  The result inherits
+        item_cost / long_thresh, plans lazily, and its t() is the ordinary sort (a sample is not symmetric).  One
+        launch pair on the device (`gcn_csr_sample_rows`: no sort, no workspace); host reads: the 8-byte entry
+        count, and the range check of `rows` when given."""
+        from .sampling import sample_neighbors
+        return sample_neighbors(self, fanout, by=by, seed=seed, stream=stream, rows=rows, keep_diagonal=keep_diagonal,
+                                rescale=rescale)
+
     def row_normalize_(self):
         """In place D^-1 · A on the device (`gcn_row_normalize_device`): the reference's
         `normalize(mx)` (pygcn/utils.py:390-397); rows whose sum has an infinite float32

@@ -33,8 +33,13 @@ VALUE_FLAGS = (
     ("--dataset", str, "cora", "Dataset name inside --path."),
     ("--normalization", str, "row", "Adjacency normalisation: row = D^-1 (A + I), the reference's; sym = "
                                     "D^-1/2 (A + I) D^-1/2, Kipf & Welling's (extension)."),
+    ("--fanout", int, 0, "Train every epoch on a fresh neighbour sample of at most this many stored entries per "
+                         "row, the kept values rescaled to the row's sum (extension, CSRGraph.sample_neighbors); "
+                         "validation and test keep the full graph.  0 = off."),
+    ("--sample_by", str, "uniform", "How --fanout chooses: uniform, weight (proportional to the entry's value) "
+                                    "or strongest (the largest values, the same every epoch)."),
 )
-CHOICES = {"--normalization": ("row", "sym")}
+CHOICES = {"--normalization": ("row", "sym"), "--sample_by": ("uniform", "weight", "strongest")}
 SWITCHES = (
     ("--no-cuda", "Disables CUDA training (unsupported here: the path is HIP-only)."),
     ("--fastmode", "Validate during training pass."),
@@ -74,11 +79,22 @@ class Run:
                                     weight_decay=args.weight_decay)
         self.fastmode = args.fastmode
         self.restrict_forward = args.restrict_forward
-        if self.restrict_forward or args.share_transpose:    # (both take the prepared handle, not the COO tensor)
+        self.fanout, self.sample_by, self.seed = args.fanout, args.sample_by, args.seed
+        if self.fanout < 0:
+            raise SystemExit("--fanout must be at least 1 (0 = off)")
+        # (all three take the prepared handle, not the COO tensor)
+        if self.restrict_forward or args.share_transpose or self.fanout:
             from pygcn_amd.graph import as_graph
             self.adj = as_graph(self.adj)
         if args.share_transpose:
             self.adj.share_transpose()
+
+    def train_adj(self, number):
+        """The adjacency of training epoch `number`: the graph, or with --fanout its sample of that epoch — the
+        epoch number is the stream of the draw, the run's seed its seed."""
+        if not self.fanout:
+            return self.adj
+        return self.adj.sample_neighbors(self.fanout, by=self.sample_by, seed=self.seed, stream=number, rescale="sum")
 
     def score(self, log_probs, name):
         rows = self.split[name]
@@ -94,7 +110,7 @@ class Run:
         rows = self.split["train"]
         if self.restrict_forward:
             return self.restricted_epoch(number, started, rows)
-        train_rows, log_probs = self.model(self.features, self.adj, rows=rows, keep_full=True)
+        train_rows, log_probs = self.model(self.features, self.train_adj(number), rows=rows, keep_full=True)
         loss, acc = nll_loss(train_rows, self.labels[rows]), accuracy(train_rows, self.labels[rows])
         loss.backward()
         self.opt.step()
@@ -106,16 +122,17 @@ class Run:
               % (number, loss.item(), acc.item(), val_loss.item(), val_acc.item(),
                  time.time() - started))
 
-    def restricted_rows(self, name):
+    def restricted_rows(self, name, adj=None):
         """Log-probabilities of the split's rows from a forward pass on their receptive field only."""
-        return self.model(self.features, self.adj, rows=self.split[name], restrict_forward=True)
+        return self.model(self.features, self.adj if adj is None else adj, rows=self.split[name],
+                          restrict_forward=True)
 
     def restricted_epoch(self, number, started, rows):
         """The epoch with --restrict_forward: no pass forms the full matrix, so validation is a restricted
         pass of its own over idx_val — after the step with dropout off, or, under --fastmode, with the
         parameters and the mode of the training pass (upstream validates on that pass's output there; with
         dropout the mask is a fresh draw)."""
-        train_rows = self.restricted_rows("train")
+        train_rows = self.restricted_rows("train", self.train_adj(number))
         loss, acc = nll_loss(train_rows, self.labels[rows]), accuracy(train_rows, self.labels[rows])
         loss.backward()
         val_labels = self.labels[self.split["val"]]
