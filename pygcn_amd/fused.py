@@ -86,7 +86,8 @@ class RowSets:
     """What the backward pass needs to know about the loss rows R, computed ONCE per
     (graph, rows tensor): R sorted and unique, R2 = the columns that occur in rows R of Â (= the
     rows of Âᵀ·grad_pre2 that can be non-zero) with its bitmap / count, and `at_block` = the
-    [|R2|, |R|] block of Âᵀ the layer-2 backward product runs on."""
+    [|R2|, |R|] block of Âᵀ the layer-2 backward product runs on.  The block's values, and the blocks of
+    restricted(), follow in-place edits of graph.val (row_sets() -> follow_values)."""
 
     def __init__(self, graph, rows):
         dev, n = graph.device, graph.shape[0]
@@ -111,8 +112,12 @@ class RowSets:
         rp = torch.zeros(self.n2 + 1, dtype=torch.int64, device=dev)
         if total:
             torch.cumsum(torch.bincount(dst, minlength=self.n2), 0, out=rp[1:])
+        # The block's VALUES follow graph.val (follow_values); rows2, hint2 and every schedule hang on the
+        # pattern alone.
+        self._val_from = idx[order]                # position in graph.val of every entry of the block
+        self._val_version = graph.val._version
         self.at_block = CSRGraph(rp.to(torch.int32 if total < 2 ** 31 - 1 else torch.int64),
-                                 src[order].to(torch.int32), graph.val[idx][order].contiguous(),
+                                 src[order].to(torch.int32), graph.val.detach().index_select(0, self._val_from),
                                  (self.n2, self.n_u))
         mask2 = torch.zeros(graph.shape[1], dtype=torch.bool, device=dev)
         mask2[self.rows2] = True
@@ -120,6 +125,14 @@ class RowSets:
 
     _restricted = None       # (graph.val version, a_rows2, a_block), built by restricted()
     _input_product = None    # (weakref of X, its version, graph.val version, a_rows2·X): input_product(.., rs)
+
+    def follow_values(self, graph):
+        """at_block's values again from graph.val when that was edited in place since they were gathered: one
+        index_select into the block's own array (same address: its schedules stay), no host read.  An unedited
+        graph costs the comparison of two host integers."""
+        if self._val_version != graph.val._version:
+            torch.index_select(graph.val.detach(), 0, self._val_from, out=self.at_block.val)
+            self._val_version = graph.val._version
 
     def restricted(self, graph):
         """The two row blocks of Â the RESTRICTED forward pass multiplies with (GCN2RestrictedFunction),
@@ -161,6 +174,7 @@ def row_sets(graph, rows):
         if len(per_graph) >= 4:
             per_graph.clear()
         rs = per_graph[key] = (RowSets(graph, rows), rows)     # (keeps `rows` alive: ptr stays unique)
+    rs[0].follow_values(graph)
     return rs[0]
 
 
@@ -295,7 +309,7 @@ def _gcn2_forward(ctx, x, w1, b1, w2, b2, graph, dropout_p, seed, rs=None):
     restricted = rs is not None
     a1, a2 = rs.restricted(graph) if restricted else (graph, graph)
     in_launch = {} if restricted else {"dropout_p": dropout_p, "seed": seed}
-    ctx.graph = graph
+    _spmm.keep_graph(ctx, graph)
     fw = ctx.fw = _forward_record(dropout_p, b1, b2)
     # bounds of max|operand| for the scaled fp16 GEMMs (set_gemm_scheme("h2") only; the default
     # three-part bf16 GEMMs need none), without a pass over the data:
@@ -489,6 +503,7 @@ def _gcn2_backward(ctx, x, w1, w2, h1, logp, grad, needs, rs=None, restricted=Fa
     Nothing of size [N, ·] exists on the rows route before the layer-1 operand; the dense route is the
     minimum number of full-height sweeps, each stage handing the next what it needs; none synchronises
     with the host."""
+    _spmm.graph_unedited(ctx)
     fw, graph = ctx.fw, ctx.graph
     need_x, need_w1, need_b1, need_w2, need_b2 = needs
     dev, dt = h1.device, h1.dtype
@@ -614,6 +629,7 @@ class GCN2Function(torch.autograd.Function):
         x, w1, w2, h1, logp = ctx.saved_tensors
         needs = ctx.needs_input_grad[:5]
         if isinstance(grad, RowGrad) and grad.rows.numel() and grad.values.dtype == logp.dtype:
+            _spmm.graph_unedited(ctx)             # (before the row sets follow the values)
             rs = row_sets(ctx.graph, grad.rows)
             grads = _gcn2_backward_rows(ctx, x, w1, w2, h1, logp.index_select(0, rs.rows_user), rs,
                                         grad.values, needs)

@@ -65,7 +65,9 @@ class CSRGraph:
     def __init__(self, rowptr, col, val, shape, item_cost=0, long_thresh=0, validate=True):
         """`validate` (default on; one-off, a few device reductions) checks what the kernels
         assume — monotone row pointers ending at nnz and 0 <= col < n_cols — because an
-        out-of-range index would be an out-of-bounds gather on the GPU."""
+        out-of-range index would be an out-of-bounds gather on the GPU.
+        `val` may be edited in place between steps (torch ops, row_normalize_, sym_normalize_): every cache
+        that hangs on the values follows its version counter ("What hangs on a graph's values")."""
         for name, t in (("rowptr", rowptr), ("col", col), ("val", val)):
             _require_cuda(t, name)
         n_rows, n_cols = int(shape[0]), int(shape[1])
@@ -482,14 +484,14 @@ class CSRGraph:
     def sym_normalize_(self):
         """In place D^-½ · A · D^-½ on the device (`gcn_sym_normalize_device`), Kipf & Welling's normalisation:
         entry (i, j) becomes w / sqrt(d_i · d_j) with the row sums d in double; a zero product gives 0, a NaN stays in
-        its row and column.  Bitwise symmetric weights stay bitwise symmetric.  Square matrices only.  Invalidates
-        the cached transpose."""
+        its row and column.  Bitwise symmetric weights stay bitwise symmetric.  Square matrices only.  Counts as
+        an in-place edit of `val` (_values_edited)."""
         if self.shape[0] != self.shape[1]:
             raise RuntimeError(f"sym_normalize_: the matrix must be square, got {self.shape}")
         _native.launch("gcn_sym_normalize_device", self.device, self.rowptr.data_ptr(),
                        int(self.rowptr.dtype == torch.int64), self.col.data_ptr(), self.val.data_ptr(), self.shape[0],
                        workspace=_native.lib().gcn_sym_normalize_workspace_bytes(self.shape[0]))
-        self._t = self._share = None
+        self._values_edited()
         return self
 
     def take_rows(self, rows, col_map=None, n_cols=None):
@@ -569,20 +571,28 @@ class CSRGraph:
     def row_normalize_(self):
         """In place D^-1 · A on the device (`gcn_row_normalize_device`): the reference's
         `normalize(mx)` (pygcn/utils.py:390-397); rows whose sum has an infinite float32
-        reciprocal (0, or a subnormal below 2^-128) become 0, as there.  Invalidates the cached
-        transpose."""
+        reciprocal (0, or a subnormal below 2^-128) become 0, as there.  Counts as an in-place
+        edit of `val` (_values_edited)."""
         _native.launch("gcn_row_normalize_device", self.device, self.rowptr.data_ptr(),
                        int(self.rowptr.dtype == torch.int64), self.val.data_ptr(), self.shape[0])
-        self._t = self._share = None
+        self._values_edited()
         return self
+
+    def _values_edited(self):
+        """After a native launch that wrote `val` through its address: moves val's version counter, as a torch
+        in-place op would have, so that everything keyed on it — here, in fused.py, in a caller's own code —
+        sees the edit; drops what this handle holds of the old values."""
+        torch.autograd.graph.increment_version(self.val)
+        self._t = self._share = self._inf_norm = None
 
     def inf_norm(self):
         """‖A‖∞ = the largest absolute row sum, as a DEVICE float tensor [1] (computed once): with
         it, max|A·B| <= ‖A‖∞ · max|B| bounds a product's output without a pass over it."""
         if self._inf_norm is None or self._inf_norm[0] != self.val._version:
-            row = self.coo()[0]
-            sums = torch.zeros(self.shape[0], dtype=torch.float32, device=self.device).index_add_(
-                0, row, self.val.abs())
+            # a segmented reduction — one fixed summation order per row — and not index_add_: the order of its
+            # float atomics, and with it the last bits of the norm of a hub row and of every product scaled
+            # by this bound, differed from one handle on the same arrays to the next
+            sums = torch.segment_reduce(self.val.detach().abs(), "sum", offsets=self.rowptr, axis=0, unsafe=True)
             top = sums.max() if sums.numel() else sums.sum()
             self._inf_norm = (self.val._version, (top * 1.00001).reshape(1))
         return self._inf_norm[1]
@@ -759,17 +769,20 @@ _ADJ_CACHE_ATTR = "_pygcn_amd_graph"
 
 def as_graph(adj):
     """Accept what the reference's layer accepts for `adj` and return the prepared handle.
-    torch sparse COO/CSR tensors are converted ONCE and the handle is cached on the tensor."""
+    torch sparse COO/CSR tensors are converted ONCE per state of their values and the handle is cached on
+    the tensor, beside the version counter of the values it was built from: an in-place edit of
+    `adj._values()` / `adj.values()` converts again."""
     if isinstance(adj, CSRGraph):
         return adj
     if isinstance(adj, torch.Tensor) and adj.layout in (torch.sparse_coo, torch.sparse_csr):
-        g = getattr(adj, _ADJ_CACHE_ATTR, None)
-        if g is None:
+        version = (adj._values() if adj.layout == torch.sparse_coo else adj.values())._version
+        hit = getattr(adj, _ADJ_CACHE_ATTR, None)
+        if hit is None or hit[1] != version:
             _require_cuda(adj, "adj")
-            g = CSRGraph.from_torch(adj)
+            hit = (CSRGraph.from_torch(adj), version)
             try:
-                setattr(adj, _ADJ_CACHE_ATTR, g)
+                setattr(adj, _ADJ_CACHE_ATTR, hit)
             except AttributeError:
                 pass
-        return g
+        return hit[0]
     raise RuntimeError(f"adj must be a CSRGraph or a torch sparse tensor, got {type(adj)}")

@@ -541,6 +541,26 @@ def check_fused_epilogue(relu, dropout_p, log_softmax=False):
         raise RuntimeError("log_softmax cannot be combined with the fused ReLU / dropout")
 
 
+def keep_graph(ctx, graph):
+    """`ctx.graph` of an autograd node, with the version counter of the graph's values beside it: the graph is
+    no saved tensor, so autograd's own check does not see an in-place edit of `graph.val` between the forward
+    pass and its backward pass (graph_unedited does)."""
+    ctx.graph = graph
+    ctx.val_version = graph.val._version if isinstance(graph, CSRGraph) else None
+
+
+def graph_unedited(ctx):
+    """Raises, in a backward pass, when ctx.graph's values were edited in place since keep_graph(): the saved
+    activations belong to the old matrix, the transpose and the row blocks would come from the new one."""
+    graph = ctx.graph
+    if ctx.val_version is not None and graph.val._version != ctx.val_version:
+        raise RuntimeError(
+            f"pygcn_amd: the values of {graph!r}, which this backward pass needs for gradient computation, have "
+            f"been modified by an inplace operation: graph.val is at version {graph.val._version}; expected version "
+            f"{ctx.val_version} instead. Edit the values (val.mul_, row_normalize_, sym_normalize_, an optimizer "
+            "step) between steps, not between a forward pass and its backward pass.")
+
+
 class SpMMFunction(torch.autograd.Function):
     """out = dropout(relu(A · B + bias)) with every stage optional and fused into the kernel's
     store;  grad_B = A^T · grad_pre;  grad_bias = column sums of grad_pre, where
@@ -552,7 +572,7 @@ class SpMMFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, graph, B, bias, relu=False, dropout_p=0.0, seed=0):
         check_fused_epilogue(relu, dropout_p)
-        ctx.graph = graph
+        keep_graph(ctx, graph)
         ctx.has_bias = bias is not None
         ctx.relu = bool(relu)
         ctx.scale = dropout_scale(dropout_p)
@@ -563,6 +583,7 @@ class SpMMFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
+        graph_unedited(ctx)
         grad_B = None
         out = ctx.saved_tensors[0] if ctx.relu else None
         grad_out, grad_bias, hint = _grad_pre_and_bias(grad_out, out, ctx.relu, ctx.scale,
@@ -616,7 +637,7 @@ class GraphConvFunction(torch.autograd.Function):
     def forward(ctx, input, weight, bias, graph, relu=False, dropout_p=0.0, seed=0,
                 log_softmax=False):
         check_fused_epilogue(relu, dropout_p, log_softmax)
-        ctx.graph = graph
+        keep_graph(ctx, graph)
         ctx.relu = bool(relu)
         ctx.log_softmax = bool(log_softmax)
         ctx.scale = dropout_scale(dropout_p)
@@ -736,6 +757,7 @@ class GraphConvFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         from .rowgrad import RowGrad
+        graph_unedited(ctx)
         if isinstance(grad_out, RowGrad):
             res = GraphConvFunction._backward_rows(ctx, grad_out)
             if res is not None:

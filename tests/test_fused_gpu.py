@@ -586,11 +586,16 @@ def test_input_product_cache_is_bitwise_neutral_and_notices_changes(dev):
         x.mul_(1.0)                                           # version bump: must recompute
         third = step()
         n_fwd.append(sum(1 for r in launches if r[0] == "fwd"))
+        g.val.mul_(1.0)                                       # the adjacency's values: the same bits, a new version
+        fourth = step()
+        n_fwd.append(sum(1 for r in launches if r[0] == "fwd"))
     finally:
         fused.set_input_product_cache(False)
         S.set_timing_records(None)
-    for got in (first, second, third):
+    for got in (first, second, third, fourth):
         assert torch.equal(got[0], base[0])
         for a, b in zip(got[1], base[1]):
             assert torch.equal(a, b)
-    assert n_fwd[0] == 2 + 1 and n_fwd[1] == n_fwd[0] + 2     # 2 products, then 1 (cached), then 2 again
+    # 2 products, then 1 (cached), then 2 again, and 2 after the edit of the adjacency (an edit that CHANGES the
+    # values, judged against a fresh handle: tests/test_graph_state_gpu.py)
+    assert n_fwd[0] == 2 + 1 and n_fwd[1] == n_fwd[0] + 2 and n_fwd[2] == n_fwd[1] + 2
