@@ -792,6 +792,10 @@ int gcn_attn_backward(int dtype, const void *h, const float *ds, const float *ke
  *                       p = 0 gives key +0: such a vertex is taken after every positive one, lowest index first.
  *                       A negative or non-finite p is the CALLER'S ERROR and is not detected (torch.multinomial
  *                       raises, which needs a host read).  keys may alias p.
+ *   gcn_race_keys_dev   gcn_race_keys with the seed read from *seed_dev (DEVICE uint64, 8-byte aligned) when the
+ *                       kernel RUNS, as gcn_epilogue.seed_dev is: a launch captured into a hipGraph draws anew on
+ *                       every replay if the graph also advances *seed_dev.  The bits of gcn_race_keys(seed = *seed_dev).
+ *                       (Added without moving the ABI number.)
  * Integer atomics and fixed-order scans only: two runs give the same bytes, and window j of a batched call is,
  * bit for bit, the batch = 1 call on a contiguous copy of the window.  Tensors 4-byte aligned (GCN_E_ALIGN).
  * Scratch of gcn_select_kth and gcn_select_indices, which the caller need not initialise:
@@ -807,6 +811,8 @@ int gcn_select_indices(const float *keys, int64_t n_rows, int64_t batch, int64_t
                        const int32_t *count_gt, int64_t *idx, void *workspace, size_t workspace_bytes, void *stream);
 int gcn_topk_flag(const float *s, int64_t n_rows, int64_t batch, const float *thr, float *flag, void *stream);
 int gcn_race_keys(const float *p, int64_t n_rows, int64_t batch, uint64_t seed, float *keys, void *stream);
+int gcn_race_keys_dev(const float *p, int64_t n_rows, int64_t batch, const uint64_t *seed_dev, float *keys,
+                      void *stream);
 
 /*
  * The input side of the fork's evaluator GCN_OVER_MLP (reference pygcn/models.py:333-355, PoolLayer :267-286) as one

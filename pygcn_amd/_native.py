@@ -145,6 +145,7 @@ SIGNATURES = {
     "gcn_select_indices": (i, [p, i64, i64, i64, p, p, p, p, sz, p]),
     "gcn_topk_flag": (i, [p, i64, i64, p, p, p]),
     "gcn_race_keys": (i, [p, i64, i64, ctypes.c_uint64, p, p]),
+    "gcn_race_keys_dev": (i, [p, i64, i64, p, p, p]),
     "gcn_eval_workspace_bytes": (sz, [i64, i64, i64, i64]),
     "gcn_eval_ingest": (i, [p, p, i64, i64, i64, i64, p, p, p, p, p, sz, p]),
     "gcn_eval_ingest_backward": (i, [p, p, p, p, p, i64, i64, i64, i64, p, p, p]),

@@ -334,8 +334,14 @@ __global__ __launch_bounds__(256) void topk_flag_kernel(const float *s, const fl
 
 // a thread draws the four vertices 4q .. 4q + 3 of its window from one call of the dropout's generator
 __global__ __launch_bounds__(256) void race_keys_kernel(const float *p, float *keys, int64_t n_rows,
-                                                        uint32_t seed_lo, uint32_t seed_hi)
+                                                        uint32_t seed_lo, uint32_t seed_hi,
+                                                        const uint64_t *__restrict__ seed_dev)
 {
+    if (seed_dev != nullptr) {     // the seed as of execution time (a captured launch), as gcn_epilogue.seed_dev
+        const uint64_t sd = *seed_dev;
+        seed_lo = (uint32_t)sd;
+        seed_hi = (uint32_t)(sd >> 32);
+    }
     const int64_t w = (int64_t)blockIdx.y * n_rows;
     const int64_t groups = (n_rows + 3) >> 2;
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < groups; q += (int64_t)gridDim.x * 256) {
@@ -457,7 +463,20 @@ int gcn_race_keys(const float *p, int64_t n_rows, int64_t batch, uint64_t seed, 
     if ((uintptr_t)p % 4 != 0 || (uintptr_t)keys % 4 != 0)
         return bad(who, GCN_E_ALIGN, "p, keys: 4-byte alignment required");
     hipLaunchKernelGGL(race_keys_kernel, flat_grid((n_rows + 3) / 4, batch), dim3(256), 0, (hipStream_t)stream, p, keys,
-                       n_rows, (uint32_t)seed, (uint32_t)(seed >> 32));
+                       n_rows, (uint32_t)seed, (uint32_t)(seed >> 32), (const uint64_t *)nullptr);
+    return launched(who);
+}
+
+int gcn_race_keys_dev(const float *p, int64_t n_rows, int64_t batch, const uint64_t *seed_dev, float *keys,
+                      void *stream)
+{
+    const char *who = "gcn_race_keys_dev";
+    if (int rc = check_shape(who, n_rows, batch)) return rc;
+    if (p == nullptr || keys == nullptr || seed_dev == nullptr) return bad(who, GCN_E_BADARG, "NULL pointer");
+    if ((uintptr_t)p % 4 != 0 || (uintptr_t)keys % 4 != 0 || (uintptr_t)seed_dev % 8 != 0)
+        return bad(who, GCN_E_ALIGN, "seed_dev: 8-byte, p, keys: 4-byte alignment required");
+    hipLaunchKernelGGL(race_keys_kernel, flat_grid((n_rows + 3) / 4, batch), dim3(256), 0, (hipStream_t)stream, p, keys,
+                       n_rows, 0u, 0u, seed_dev);
     return launched(who);
 }
 

@@ -214,9 +214,11 @@ def input_product(graph, x, rs=None):
     """z = Â·X for the layer-1 input, from the per-graph cache when set_input_product_cache(True), X
     needs no gradient, and neither the graph's values nor X changed since it was computed.  With `rs`:
     z_c = Â[R2, :]·X, the compact input of the restricted pass, under the same rule; that product
-    hangs on the row sets (`rs._input_product`) where the full one hangs on the graph."""
+    hangs on the row sets (`rs._input_product`) where the full one hangs on the graph.  While the stream
+    is being captured into a hipGraph the cache is neither consulted nor filled: the product is recorded
+    in the graph, so a replay follows in-place refills of X."""
     a, holder = (graph, graph) if rs is None else (rs.restricted(graph)[0], rs)
-    if not _CACHE_INPUT_PRODUCT or x.requires_grad:
+    if not _CACHE_INPUT_PRODUCT or x.requires_grad or torch.cuda.is_current_stream_capturing():
         return spmm_csr(a, x)
     hit = getattr(holder, "_input_product", None)
     if (hit is not None and hit[0]() is x and hit[1] == x._version and hit[2] == graph.val._version):

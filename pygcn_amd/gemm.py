@@ -155,7 +155,7 @@ def gemm_xw256(X, W, x_bound=None, y_absmax=None, rows=None, mask_src=None, mask
         # no bound known: one reduction pass over X (1.4 ms at M = 10^7) and the 5.4 ms kernel
         # still beat the 7.5 ms three-part kernel — and keep full accuracy for tiny operands,
         # where the third bf16 part would fall into the denormals
-        x_bound = torch.linalg.vector_norm(X.detach(), ord=float("inf")).reshape(1)
+        x_bound = absmax_now(X)
     ep = None
     if has_fwd_ep or mask_src is not None:
         by_bits = mask_bits is not None
@@ -364,10 +364,10 @@ def weight_grad_rows(A, G, rows_a=None, rows_g=None, a_bound=None, g_bound=None,
         # (no bound supplied: a reduction pass — over the LISTED rows only, the others may hold anything)
         if a_bound is None:
             src = A.detach()[:n_list] if rows_a is None else A.detach().index_select(0, rows_a[:n_list].long())
-            a_bound = torch.linalg.vector_norm(src, ord=float("inf")).reshape(1)
+            a_bound = absmax_now(src)
         if g_bound is None:
             src = G.detach()[:n_list] if rows_g is None else G.detach().index_select(0, rows_g[:n_list].long())
-            g_bound = torch.linalg.vector_norm(src, ord=float("inf")).reshape(1)
+            g_bound = absmax_now(src)
         name, bounds = "gcn_gemm_atg256_f32", (a_bound.data_ptr(), g_bound.data_ptr())
     _native.launch(name, A.device, A.data_ptr(), A.stride(0), lists[0].data_ptr(), G.data_ptr(), G.stride(0),
                    lists[1].data_ptr(), n_list, *bounds, out.data_ptr(), out.stride(0), *sums,
@@ -393,13 +393,45 @@ def _absmax_put(kind, t, val):
     _absmax[key] = live[-3:] + [(weakref.ref(t), t._version, val)]
 
 
+def _absmax_staged(t):
+    """max|t| as a DEVICE float [1] — the value of torch.linalg.vector_norm(t, inf), a maximum being exact in any
+    order — by reductions of at most a row each: per row of t, then over groups of 128 until one group is left.
+    For a launch recorded in a hipGraph: torch's one-output reduction of a large tensor splits the output over
+    blocks that meet through a zeroed counter, and replayed from a graph that begins with it, after any kernel on
+    the launching stream, it left its result unwritten (profiles/capture_coverage.md, finding 4); a reduction whose
+    every output belongs to one block has no such counter."""
+    v = t.detach()
+    if v.dim() >= 2 and v.shape[-1] <= 4096:
+        v = torch.linalg.vector_norm(v.reshape(-1, v.shape[-1]), ord=float("inf"), dim=1)
+    else:
+        v = v.reshape(-1).abs()
+    while v.numel() > 128:
+        pad = (-v.numel()) % 128
+        if pad:
+            v = torch.nn.functional.pad(v, (0, pad))
+        v = v.view(-1, 128).amax(dim=1)
+    return v.amax().float().reshape(1)
+
+
+def absmax_now(t):
+    """max|t| as a DEVICE float [1] by one reduction pass, for every bound formed where none is known: torch's
+    vector_norm, and _absmax_staged (the same bits) while the stream is being captured into a hipGraph."""
+    if t.is_cuda and torch.cuda.is_current_stream_capturing():
+        return _absmax_staged(t)
+    return torch.linalg.vector_norm(t.detach(), ord=float("inf")).reshape(1)
+
+
 def absmax_cached(t):
     """max|t| as a DEVICE float tensor [1], computed once per (tensor object, version): for operands
     that stay constant across steps (the feature matrix).  A few entries per device (an eval-mode
     forward pass sees every layer's input as "constant": they must not evict each other), each
     holding a weak reference to the tensor OBJECT — a new tensor that happens to reuse the storage
     address of a freed one can never inherit its bound (a bound that is too small would overflow
-    the fp16 parts)."""
+    the fp16 parts).  While the stream is being captured into a hipGraph the cache is neither consulted
+    nor filled: a replay follows in-place refills of t, which a bound computed before the capture would
+    not, so the reduction is recorded in the graph."""
+    if t.is_cuda and torch.cuda.is_current_stream_capturing():
+        return _absmax_staged(t)
     val = _absmax_get("computed", t)
     if val is None:
         val = torch.linalg.vector_norm(t.detach(), ord=float("inf")).float().reshape(1)

@@ -24,7 +24,7 @@ All of them take and return fp32 [k, n] (one row per sample or window) on the HI
 import torch
 
 from . import _native
-from .spmm import next_dropout_seed
+from .spmm import dropout_seed_for
 
 
 def _rows(t, what):
@@ -65,10 +65,17 @@ def flag_above(s, thr, out=None):
 
 def race_keys(p, seed):
     """fp32 [k, n]: p / E with E ~ Exp(1) drawn from Philox4x32-10 at (seed, window, vertex) — the stream
-    include/gcn_spmm.h states.  `p` must be finite and >= 0 (not checked: that would read the device)."""
+    include/gcn_spmm.h states.  `p` must be finite and >= 0 (not checked: that would read the device).  A
+    1-element int64 DEVICE tensor as `seed` is read when the kernel runs (C-ABI gcn_race_keys_dev: a launch
+    captured into a hipGraph, spmm.dropout_seed_for); the keys are those of its value as a host seed."""
     k, n = _rows(p, "race_keys")
     keys = torch.empty_like(p)
-    _native.launch("gcn_race_keys", p.device, p.data_ptr(), n, k, int(seed) & 0xFFFFFFFFFFFFFFFF, keys.data_ptr())
+    if isinstance(seed, torch.Tensor):
+        if seed.dtype != torch.int64 or seed.numel() != 1 or seed.device != p.device:
+            raise RuntimeError("race_keys: a tensor seed must be one int64 on the operand's device")
+        _native.launch("gcn_race_keys_dev", p.device, p.data_ptr(), n, k, seed.data_ptr(), keys.data_ptr())
+    else:
+        _native.launch("gcn_race_keys", p.device, p.data_ptr(), n, k, int(seed) & 0xFFFFFFFFFFFFFFFF, keys.data_ptr())
     return keys
 
 
@@ -141,8 +148,9 @@ def sample_without_replacement(probs, NN, seed=None):
     torch's own implementation or a host read: int64 [NN] for probs [N], [k, NN] for [k, N], on probs'
     device, in DRAW ORDER (descending race key, the lower index first on equal keys).  The law is
     torch.multinomial's (module docstring); the stream is this project's, fixed by `seed`.  seed=None draws
-    one from the device's generator as a fused dropout launch does (spmm.next_dropout_seed), so
-    torch.manual_seed reproduces a run.  probs must be finite and >= 0 — NOT checked on the device, where
+    one from the device's generator as a fused dropout launch does (spmm.dropout_seed_for), so
+    torch.manual_seed reproduces a run; while the stream is being captured into a hipGraph that is the
+    device-resident seed the capture advances, so every replay draws anew.  probs must be finite and >= 0 — NOT checked on the device, where
     torch.multinomial would synchronise to raise; a vertex with probability 0 is picked only when NN exceeds
     the number of positive ones, lowest index first.  CPU tensors go to torch.multinomial."""
     if probs.dim() not in (1, 2):
@@ -153,7 +161,7 @@ def sample_without_replacement(probs, NN, seed=None):
     if not probs.is_cuda:
         return torch.multinomial(probs, NN, replacement=False)
     p = probs.detach().to(torch.float32).reshape(-1, n).contiguous()
-    keys = race_keys(p, next_dropout_seed(probs.device) if seed is None else seed)
+    keys = race_keys(p, dropout_seed_for(p) if seed is None else seed)
     idx = topk_indices(keys, NN, *kth_largest(keys, NN))
     # the NN survivors in draw order: a stable descending sort of their keys keeps ascending indices on ties
     order = torch.sort(keys.gather(1, idx), dim=1, descending=True, stable=True).indices

@@ -11,7 +11,7 @@ fallback exists: non-HIP tensors or a missing library raise.
 import torch
 
 from . import _native, tuning
-from .gemm import (_dense_forward, _dense_grads, _seed_fields, _weight_grad, absmax_cached, gemm_bf16,
+from .gemm import (_dense_forward, _dense_grads, _seed_fields, _weight_grad, absmax_cached, absmax_now, gemm_bf16,
                    gemm_handwritten, gemm_needs_bounds, gemm_xw256, known_absmax, layer_gemm,
                    layer_gemm_reassociable, padded_row_list, remember_absmax, weight_grad_rows)
 # (names of gemm.py that callers reach as pygcn_amd.spmm.<name>: bench.py and tests/conftest.py the scheme
@@ -707,7 +707,7 @@ class GraphConvFunction(torch.autograd.Function):
             if not (need_in or need_w):
                 return None, None, grad_bias, None, None, None, None, None
             grad_sup = spmm_csr(rs.at_block, gp.contiguous(), tag="bwd")          # [|R2|, Fout], compact
-            gs_bound = (graph.t().inf_norm() * torch.linalg.vector_norm(gp, ord=float("inf")) * 1.0001) \
+            gs_bound = (graph.t().inf_norm() * absmax_now(gp) * 1.0001) \
                 if f32 else None
             grad_w = grad_in = None
             if need_w:
@@ -797,7 +797,7 @@ class GraphConvFunction(torch.autograd.Function):
                 if ctx.z_bound is not None:      # |mask(grad_out)| <= scale * max|grad_out|
                     g_bound = known_absmax(grad_out)
                     g_bound = g_bound * ctx.scale if g_bound is not None else \
-                        torch.linalg.vector_norm(grad_pre, ord=float("inf")).reshape(1)
+                        absmax_now(grad_pre)
                 grad_w = _weight_grad(z, grad_pre, ctx.z_bound, g_bound)
             return None, grad_w, grad_bias, None, None, None, None, None
         c_flags = rows = None

@@ -12,7 +12,8 @@ import torch.nn as nn
 import _select_ref as R
 from conftest import ROOT, assert_normwise, assert_parity, load_golden
 
-NAMES = ("gcn_select_workspace_bytes", "gcn_select_kth", "gcn_select_indices", "gcn_topk_flag", "gcn_race_keys")
+NAMES = ("gcn_select_workspace_bytes", "gcn_select_kth", "gcn_select_indices", "gcn_topk_flag", "gcn_race_keys",
+         "gcn_race_keys_dev")
 P8 = np.array([.30, .22, .15, .12, .09, .06, .04, .02], np.float32)
 
 

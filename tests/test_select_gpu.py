@@ -429,14 +429,16 @@ def test_c_abi_argument_errors():
     need = L.gcn_select_workspace_bytes(n, k)
     assert need == k * (3 * 2048 + 8 + 2) * 4
     ws = torch.empty(need + 16, dtype=torch.uint8, device=DEV)
-    kp, op, tp, cp, ip, wp = (t.data_ptr() for t in (keys, out, thr, cnt, idx, ws))
+    seed = torch.tensor([42, 0], dtype=torch.int64, device=DEV)
+    kp, op, tp, cp, ip, wp, sp = (t.data_ptr() for t in (keys, out, thr, cnt, idx, ws, seed))
 
-    def calls(n=n, k=k, m=m, kp=kp, tp=tp, ip=ip, wp=wp, need=need):
+    def calls(n=n, k=k, m=m, kp=kp, tp=tp, ip=ip, wp=wp, need=need, sp=sp):
         return {
             "gcn_select_kth": lambda: L.gcn_select_kth(kp, n, k, m, tp, cp, wp, need, None),
             "gcn_select_indices": lambda: L.gcn_select_indices(kp, n, k, m, tp, cp, ip, wp, need, None),
             "gcn_topk_flag": lambda: L.gcn_topk_flag(kp, n, k, tp, op, None),
             "gcn_race_keys": lambda: L.gcn_race_keys(kp, n, k, 42, op, None),
+            "gcn_race_keys_dev": lambda: L.gcn_race_keys_dev(kp, n, k, sp, op, None),
         }
 
     def expect(table, code, only=None):
@@ -456,8 +458,10 @@ def test_c_abi_argument_errors():
     expect(calls(kp=None), -1)                   # GCN_E_BADARG: NULL tensor
     expect(calls(tp=None), -1, ranked + ("gcn_topk_flag",))
     expect(calls(ip=None), -1, ("gcn_select_indices",))
+    expect(calls(sp=None), -1, ("gcn_race_keys_dev",))   # the device seed is not optional
     expect(calls(kp=kp + 2), -2)                 # GCN_E_ALIGN: a float off the 4-byte grid
     expect(calls(ip=ip + 4), -2, ("gcn_select_indices",))
+    expect(calls(sp=sp + 4), -2, ("gcn_race_keys_dev",))  # a 64-bit seed off the 8-byte grid
     expect(calls(wp=wp + 1), -2, ranked)
     expect(calls(need=need - 1), -3, ranked)     # GCN_E_WORKSPACE: one byte short, or NULL
     expect(calls(wp=None), -3, ranked)
